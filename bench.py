@@ -10,6 +10,17 @@ ranks, and rank 0 prints ONE JSON line.
 Metric (BASELINE.json): CG iter/s (whole node) on Queen_4147-shaped data
 (4.1M rows / ~330M nnz fp64; synthetic 27-pt dof-3 stencil -- no network,
 no SuiteSparse downloads), strong scaling across 1/2/4/8 MI355X.
+
+A plain run does only what the headline needs: setup, solver selection,
+warmup, the K timed iterations, the JSON line.  `--full` adds the checks
+and diagnostics that take GPU work of their own (true-residual integrity
+check, per-rank span profile).  `--dump-outputs DIR` writes what the timed
+solve returned (final iterate, residual norms) as DIR/<name>.npy so two
+builds can be compared output for output; inputs are seeded, hence
+identical from run to run for the same arguments.  `--solver auto` may
+pick classic or pipelined CG by a timing probe (mathematically equivalent,
+different rounding); DIR/solver.txt records the choice, and a comparison
+that wants the same algorithm on both sides passes `--solver` explicitly.
 """
 
 from __future__ import annotations
@@ -22,6 +33,18 @@ import time
 
 import numpy as np
 import torch
+
+# --dump-outputs: bytes of iterate written over all ranks (float64)
+DUMP_X_BYTES = 48 << 20
+
+
+def dump_sample(n: int, cap: int, seed: int) -> np.ndarray:
+    """Fixed seeded sample of ``cap`` distinct sorted indices out of
+    ``n > cap``: one uniformly drawn index from each of ``cap`` contiguous
+    strata, so the sample spans the whole vector without duplicates."""
+    edges = (np.arange(cap + 1, dtype=np.int64) * n) // cap
+    lo, hi = edges[:-1], edges[1:]
+    return lo + np.random.default_rng(seed).integers(0, hi - lo)
 
 
 def main() -> int:
@@ -65,6 +88,18 @@ def main() -> int:
                          "default keeps the assembled, memory-resident "
                          "operator so numbers reflect the sparse-matrix "
                          "workload BASELINE names)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: "
+                         "the true-residual integrity check and the "
+                         "per-rank span profile (multi-GPU, or "
+                         "ACG_BENCH_SPANS=1)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the timed solve "
+                         "returned as DIR/<name>.npy (float64): the owned "
+                         "part of the final iterate x (a fixed seeded "
+                         "sample when larger than 48 MB over all ranks) "
+                         "and the residual norms; solver.txt names the "
+                         "solver that ran (pass --solver to pin it)")
     args = ap.parse_args()
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -238,35 +273,58 @@ def main() -> int:
 
     assert res.niterations == args.steps, (res.niterations, args.steps)
 
-    # integrity check (outside the timed region): the TRUE residual of the
-    # final iterate must agree with the recursion residual the solver
+    # what the timed solve handed back: the owned part of the final iterate
+    # and the residual norms.  Every rank writes its own files; the 48 MB
+    # iterate budget is shared, larger iterates are cut to a fixed seeded
+    # sample.  solver.txt names the algorithm the auto policy timed.
+    if args.dump_outputs:
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        sfx = f"_rank{rank}" if ngpus > 1 else ""
+        cap = DUMP_X_BYTES // 8 // ngpus
+        xo = x[:S.nowned]
+        if S.nowned > cap:
+            pick = dump_sample(S.nowned, cap, 777 + rank)
+            xo = xo[torch.from_numpy(pick).to(device)]
+        if rank == 0:
+            with open(os.path.join(args.dump_outputs, "solver.txt"), "w") as f:
+                f.write(f"cg-{solver_kind}\n")
+        np.save(os.path.join(args.dump_outputs, f"x{sfx}.npy"),
+                xo.cpu().numpy().astype(np.float64, copy=False))
+        np.save(os.path.join(args.dump_outputs, f"residual_norms{sfx}.npy"),
+                np.array([res.bnrm2, res.r0nrm2, res.rnrm2], dtype=np.float64))
+
+    # integrity check (outside the timed region, --full): the TRUE residual
+    # of the final iterate must agree with the recursion residual the solver
     # reports -- silent corruption anywhere (kernels, halo, captured
     # graphs, collectives) would make these diverge or go non-finite.
     # (Expected benign gap: pipelined CG's recursion residual drifts a few
     # orders below the true one at tight tolerances -- textbook behaviour,
     # e.g. true 5e-11 vs recursion 2e-15 after 200 Queen iterations.)
-    tchk = torch.zeros(S.nowned, dtype=torch.float64, device=device)
-    solver._spmv_overlapped(x, tchk)
-    rloc2 = float(torch.sum((b[:S.nowned] - tchk) ** 2))
-    bloc2 = float(torch.sum(b[:S.nowned] ** 2))
-    if comm is not None:
-        import torch.distributed as dist
+    true_rel = None
+    if args.full:
+        tchk = torch.zeros(S.nowned, dtype=torch.float64, device=device)
+        solver._spmv_overlapped(x, tchk)
+        rloc2 = float(torch.sum((b[:S.nowned] - tchk) ** 2))
+        bloc2 = float(torch.sum(b[:S.nowned] ** 2))
+        if comm is not None:
+            import torch.distributed as dist
 
-        rb = torch.tensor([rloc2, bloc2], dtype=torch.float64, device=red_dev)
-        dist.all_reduce(rb, op=dist.ReduceOp.SUM)
-        rloc2, bloc2 = float(rb[0]), float(rb[1])
-    true_rel = (rloc2 / bloc2) ** 0.5 if bloc2 > 0 else float("nan")
+            rb = torch.tensor([rloc2, bloc2], dtype=torch.float64,
+                              device=red_dev)
+            dist.all_reduce(rb, op=dist.ReduceOp.SUM)
+            rloc2, bloc2 = float(rb[0]), float(rb[1])
+        true_rel = (rloc2 / bloc2) ** 0.5 if bloc2 > 0 else float("nan")
+        assert np.isfinite(true_rel), "non-finite true residual"
     recur_rel = res.rnrm2 / res.bnrm2 if res.bnrm2 > 0 else float("nan")
-    assert np.isfinite(true_rel), "non-finite true residual"
 
-    # per-rank overlap diagnosis (outside the timed region): a short
+    # per-rank overlap diagnosis (outside the timed region, --full): a short
     # profiled EAGER pass records hipEvent spans (halo / spmvA / spmvO /
     # allreduce / update) per rank and ships them on the JSON line, so the
     # first real N=8 run is diagnosable -- not just a single number.
     # (Profiling forces the eager path; the timed number above still
     # reflects the captured-graph hot loop.)
     rank_spans = None
-    if ngpus > 1 or os.environ.get("ACG_BENCH_SPANS"):
+    if args.full and (ngpus > 1 or os.environ.get("ACG_BENCH_SPANS")):
         solver.prof.enabled = True
         pres = solve(b, x.clone(), maxits=16, res_rtol=0.0)
         solver.prof.enabled = False

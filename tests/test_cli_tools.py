@@ -2,6 +2,7 @@
 
 import gzip
 import sys
+from pathlib import Path
 
 import numpy as np
 import pytest
@@ -10,6 +11,8 @@ import torch
 from acg_amd.gen import STENCIL_5PT_2D, stencil_global
 from acg_amd.io.mtx import MtxFile, read_mtx, write_mtx
 from acg_amd.utils.numfmt import parse_numfmt
+
+TOOLS = str(Path(__file__).resolve().parent.parent / "tools")
 
 
 def _poisson_mtx(tmp_path, nx=16, ny=16, name="A.mtx"):
@@ -52,7 +55,7 @@ def test_mtx_gzip(tmp_path):
 
 
 def test_mtx2bin_tool(tmp_path):
-    sys.path.insert(0, "tools")
+    sys.path.insert(0, TOOLS)
     import importlib
 
     mtx2bin = importlib.import_module("mtx2bin")
@@ -64,7 +67,7 @@ def test_mtx2bin_tool(tmp_path):
 
 
 def test_mtxpartition_tool(tmp_path):
-    sys.path.insert(0, "tools")
+    sys.path.insert(0, TOOLS)
     import importlib
 
     mtxpartition = importlib.import_module("mtxpartition")

@@ -224,7 +224,8 @@ def test_bench_2proc_end_to_end(tmp_path):
     cmd = [_sys.executable, "-m", "torch.distributed.run", "--nnodes", "1",
            "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", "29640", "bench.py", "--gpus", "2",
-           "--steps", "5", "--warmup", "2", "--grid", "14"]
+           "--steps", "5", "--warmup", "2", "--grid", "14", "--full",
+           "--dump-outputs", str(tmp_path / "dump")]
     r = subprocess.run(cmd, capture_output=True, text=True, cwd=repo,
                        env=env, timeout=420)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
@@ -234,6 +235,24 @@ def test_bench_2proc_end_to_end(tmp_path):
     assert d["value"] > 0
     assert d["config"]["solver"] in ("cg-pipelined", "cg-classic")  # auto probes
     assert d["config"]["rows"] == 3 * 14 ** 3
+    # --full extras: integrity check and one span record per rank
+    assert np.isfinite(d["config"]["rel_residual_true"])
+    assert set(d["config"]["rank_spans_us_per_call"]) == {"r0", "r1"}
+    # --dump-outputs: per-rank float64 files, owned rows add up, the norms
+    # are allreduced (equal on both ranks), solver.txt names the solver
+    dump = tmp_path / "dump"
+    assert sorted(p.name for p in dump.iterdir()) == [
+        "residual_norms_rank0.npy", "residual_norms_rank1.npy",
+        "solver.txt", "x_rank0.npy", "x_rank1.npy"]
+    xs = [np.load(dump / f"x_rank{r}.npy") for r in range(2)]
+    nr = [np.load(dump / f"residual_norms_rank{r}.npy") for r in range(2)]
+    assert all(a.dtype == np.float64 and a.ndim == 1 for a in xs)
+    assert sum(a.size for a in xs) == 3 * 14 ** 3
+    assert all(np.isfinite(a).all() for a in xs)
+    assert nr[0].dtype == np.float64 and nr[0].shape == (3,)
+    # two-term fp64 sums: ranks agree to a few ulp whatever the order
+    np.testing.assert_allclose(nr[0], nr[1], rtol=1e-12, atol=0)
+    assert (dump / "solver.txt").read_text().strip() == d["config"]["solver"]
 
 
 @pytest.mark.gpu

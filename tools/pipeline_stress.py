@@ -29,7 +29,7 @@ for t in range(6):
                         "--solver", solver, "--partition-method", method,
                         "--manufactured-solution", "--max-iterations", "4000",
                         "--residual-rtol", "1e-8", "-q"],
-                       capture_output=True, text=True, cwd="/root/repo",
+                       capture_output=True, text=True, cwd=_P(__file__).resolve().parent.parent,
                        timeout=300)
     tailerr = r.stderr.strip().splitlines()[-1] if r.stderr.strip() else ""
     print(f"t{t}: n={n} {solver}/{method} rc={r.returncode} | {tailerr[:90]}",

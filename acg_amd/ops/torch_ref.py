@@ -15,6 +15,9 @@ import torch
 S_RR, S_PT, S_RR_PREV, S_BNRM2 = 0, 1, 2, 3
 S_GAMMA, S_DELTA, S_GAMMA_PREV, S_ALPHA_PREV = 4, 5, 6, 7
 S_NSLOTS = 8
+# half-size of the two-phase reduction scratch (shared with kernels.hip);
+# only sell_pipe/pipelined_finalize stage partial sums in this module
+MAXG = 16384
 
 
 def alloc_scalars(device="cpu") -> torch.Tensor:
@@ -44,6 +47,21 @@ def spmv(rowptr, colidx, vals, x, y, *, rowbase: int = 0, accum: bool = False,
     if scal is not None and dotslot >= 0:
         d = torch.dot(x[sl], contrib)
         scal[dotslot] = scal[dotslot] + d if dot_accum else d
+
+
+def spmv_binned(rowptr, colidx, vals, rowlist, bins, x, y, *, rowbase: int = 0,
+                accum: bool = False, partials=None, scal=None,
+                dotslot: int = -1, dot_accum: bool = True) -> None:
+    """Row-binned CSR SpMV: ``rowlist``/``bins`` only schedule the rows on
+    the GPU; every row is still computed exactly once."""
+    if rowlist.numel() == 0:
+        return
+    spmv(rowptr, colidx, vals, x, y, rowbase=rowbase, accum=accum,
+         partials=partials, scal=scal, dotslot=dotslot, dot_accum=dot_accum)
+
+
+def zero_scalars(scal, i0: int = 0, count=None) -> None:
+    scal[i0:i0 + (count if count is not None else scal.numel() - i0)] = 0.0
 
 
 def sell_from_csr(rowptr, colidx, vals, C: int = 64, sigma: int = 1):
@@ -277,7 +295,10 @@ def bsell_from_csr(rowptr, colidx, vals, dof: int, C: int = 64):
 
 def spmv_sell(sellptr, cols, vals, nrows, x, y, *, rowbase: int = 0,
               accum: bool = False, partials=None, scal=None,
-              dotslot: int = -1, dot_accum: bool = True, C: int = 64) -> None:
+              dotslot: int = -1, dot_accum: bool = True, C: int = 64,
+              variant=None, perm=None) -> None:
+    """``variant`` only selects a kernel flavour on the GPU (same result);
+    ``perm`` maps SELL row -> matrix row (sentinel nrows on pad lanes)."""
     nslices = sellptr.numel() - 1
     assert (nrows + C - 1) // C == nslices, \
         f"SELL structure was built with a different chunk size than C={C}"
@@ -287,6 +308,11 @@ def spmv_sell(sellptr, cols, vals, nrows, x, y, *, rowbase: int = 0,
         L = (int(sellptr[s + 1]) - base) // C
         block = (vals[base:base + L * C].view(L, C)
                  * x[cols[base:base + L * C].long()].view(L, C)).sum(dim=0)
+        if perm is not None:
+            rowof = perm[s * C:(s + 1) * C].long()
+            ok = rowof < nrows
+            contrib[rowof[ok]] = block[ok]
+            continue
         hi = min(C, nrows - s * C)
         contrib[s * C:s * C + hi] = block[:hi]
     sl = slice(rowbase, rowbase + nrows)
@@ -297,6 +323,64 @@ def spmv_sell(sellptr, cols, vals, nrows, x, y, *, rowbase: int = 0,
     if scal is not None and dotslot >= 0:
         d = torch.dot(x[sl], contrib)
         scal[dotslot] = scal[dotslot] + d if dot_accum else d
+
+
+def _bsell_contrib(bptr, bcol, bvals, nnodes: int, dof: int, xg, C: int = 64):
+    """A @ xg for a Block-SELL matrix, decoding the pair-major bvals layout
+    (kernels.hip bval_off): element (j, k, lane) of a slice sits at
+    (k//2)*2C + lane*2 + k%2 inside block-column group j, the odd tail
+    k = dof^2-1 at (dof^2-1)*C + lane; k = row_in_block*dof + col_in_block."""
+    D2 = dof * dof
+    even = D2 & ~1
+    nslices = bptr.numel() - 1
+    assert (nnodes + C - 1) // C == nslices, \
+        f"BSELL structure was built with a different chunk size than C={C}"
+    contrib = torch.zeros(nnodes * dof, dtype=torch.float64, device=xg.device)
+    for s in range(nslices):
+        b0 = int(bptr[s])
+        L = (int(bptr[s + 1]) - b0) // C
+        acc = torch.zeros(C, dof, dtype=torch.float64, device=xg.device)
+        if L:
+            cb = bcol[b0:b0 + L * C].view(L, C).long()
+            v = bvals[b0 * D2:(b0 + L * C) * D2].view(L, D2 * C)
+            for k in range(D2):
+                if k < even:
+                    lo = (k >> 1) * 2 * C + (k & 1)
+                    a = v[:, lo:(k >> 1) * 2 * C + 2 * C:2]
+                else:
+                    a = v[:, even * C:even * C + C]
+                acc[:, k // dof] += (a * xg[cb * dof + k % dof]).sum(dim=0)
+        hi = min(C, nnodes - s * C)
+        contrib[s * C * dof:(s * C + hi) * dof] = acc[:hi].reshape(-1)
+    return contrib
+
+
+def spmv_bsell(bptr, bcol, bvals, nnodes: int, dof: int, x, y, *,
+               partials=None, scal=None, dotslot: int = -1,
+               dot_accum: bool = True) -> None:
+    if bptr.numel() - 1 <= 0:
+        return
+    n = nnodes * dof
+    contrib = _bsell_contrib(bptr, bcol, bvals, nnodes, dof, x)
+    y[:n] = contrib
+    if scal is not None and dotslot >= 0:
+        d = torch.dot(x[:n], contrib)
+        scal[dotslot] = scal[dotslot] + d if dot_accum else d
+
+
+def spmv_bsell_daypx(bptr, bcol, bvals, nnodes: int, dof: int, pold, rvec,
+                     pnew, y, scal, partials, dotslot: int) -> None:
+    """p_new = beta*p_old + r with beta = rr/rr_prev, y = A p_new, and
+    scal[dotslot] = (p_new, y) (matches k_spmv_bsell_daypx + reduce)."""
+    if bptr.numel() - 1 <= 0:
+        return
+    n = nnodes * dof
+    beta = _sdiv(float(scal[S_RR]), float(scal[S_RR_PREV]))
+    pn = beta * pold[:n] + rvec[:n]
+    contrib = _bsell_contrib(bptr, bcol, bvals, nnodes, dof, pn)
+    pnew[:n] = pn
+    y[:n] = contrib
+    scal[dotslot] = torch.dot(pn, contrib)
 
 
 def cg_prep_pt(scal) -> None:
@@ -353,6 +437,19 @@ def cg_fused_update(r, x, p, t, scal, partials, n) -> None:
     scal[S_RR] = torch.dot(r[:n], r[:n])
 
 
+def pcg_fused_update(r, x, p, t, z, dinv, scal, partials, n) -> None:
+    """Jacobi-PCG epilogue: alpha = rz/pt; update r,x; z = dinv*r; rotate
+    rz -> rr_prev and publish the new rz in S_RR and the true (r,r) in
+    S_GAMMA (matches k_pcg_fused_update + k_pcg_finalize)."""
+    alpha = _sdiv(float(scal[S_RR]), float(scal[S_PT]))
+    r[:n] -= alpha * t[:n]
+    x[:n] += alpha * p[:n]
+    z[:n] = dinv[:n] * r[:n]
+    scal[S_RR_PREV] = scal[S_RR].clone()
+    scal[S_RR] = torch.dot(r[:n], z[:n])
+    scal[S_GAMMA] = torch.dot(r[:n], r[:n])
+
+
 def _pipelined_coeffs(scal, first: bool):
     gamma = float(scal[S_GAMMA])
     delta = float(scal[S_DELTA])
@@ -363,7 +460,8 @@ def _pipelined_coeffs(scal, first: bool):
     return beta, alpha
 
 
-def pipelined_fused(z, t, p, x, r, w, q, scal, partials, n, first: bool) -> None:
+def pipelined_fused(z, t, p, x, r, w, q, scal, partials, n, first: bool,
+                    nt_update: bool = True) -> None:
     """Update the 6 vectors AND produce the next gamma/delta + rotate the
     scalar history (matches k_pipelined_fused + k_pipelined_finalize)."""
     beta, alpha = _pipelined_coeffs(scal, first)
@@ -377,6 +475,61 @@ def pipelined_fused(z, t, p, x, r, w, q, scal, partials, n, first: bool) -> None
     scal[S_ALPHA_PREV] = alpha
     scal[S_GAMMA] = torch.dot(r[:n], r[:n])
     scal[S_DELTA] = torch.dot(w[:n], r[:n])
+
+
+def sell_pipe(sellptr, cols, vals, nrows_pass: int, rowbase: int,
+              border_base: int, w_old, qpart, z, t, p, x, r, w_new, scal,
+              first: bool, partials, partials_off: int, mato: bool,
+              C: int = 64) -> int:
+    """One pass of the megafused pipelined iteration (matches k_sell_pipe).
+
+    The matA pass (mato=False) updates rows below ``border_base`` and
+    stores the partial q of the others into qpart[row - border_base]; the
+    matO pass adds its ghost contributions to qpart and updates those rows.
+    The pass's (r,r) and (w,r) sums go to partials[partials_off] and
+    partials[MAXG + partials_off] for :func:`pipelined_finalize`, so
+    ``partials`` needs 2*MAXG entries here; always one block per pass."""
+    if nrows_pass == 0:
+        return 0
+    q = torch.zeros(rowbase + nrows_pass, dtype=torch.float64,
+                    device=w_old.device)
+    spmv_sell(sellptr, cols, vals, nrows_pass, w_old, q, rowbase=rowbase, C=C)
+    beta, alpha = _pipelined_coeffs(scal, first)
+    rows = torch.arange(rowbase, rowbase + nrows_pass, device=w_old.device)
+    if mato:
+        upd = rows
+        qu = q[upd] + qpart[upd - border_base]
+    else:
+        defer = rows[rows >= border_base]
+        qpart[defer - border_base] = q[defer]
+        upd = rows[rows < border_base]
+        qu = q[upd]
+    zi = qu + beta * z[upd]
+    ti = w_old[upd] + beta * t[upd]
+    pi = r[upd] + beta * p[upd]
+    z[upd] = zi
+    t[upd] = ti
+    p[upd] = pi
+    x[upd] += alpha * pi
+    rn = r[upd] - alpha * ti
+    wn = w_old[upd] - alpha * zi
+    r[upd] = rn
+    w_new[upd] = wn
+    partials[partials_off] = torch.dot(rn, rn)
+    partials[MAXG + partials_off] = torch.dot(wn, rn)
+    return 1
+
+
+def pipelined_finalize(partials, nblocks: int, scal, first: bool) -> None:
+    """Rotate gamma -> gamma_prev, store alpha -> alpha_prev, publish the
+    summed partials as the new gamma/delta (matches k_pipelined_finalize)."""
+    _, alpha = _pipelined_coeffs(scal, first)
+    g = partials[:nblocks].sum()
+    d = partials[MAXG:MAXG + nblocks].sum()
+    scal[S_GAMMA_PREV] = scal[S_GAMMA].clone()
+    scal[S_ALPHA_PREV] = alpha
+    scal[S_GAMMA] = g
+    scal[S_DELTA] = d
 
 
 def pack_gather(sendbuf, x, idx) -> None:

@@ -1,0 +1,965 @@
+"""High-precision oracle for the kernel-level exactness tests.
+
+Plain helper module (not a conftest).  Three parts:
+
+* oracle arithmetic: every operation is evaluated from the ORIGINAL CSR and
+  the fp64 input vectors in ``np.longdouble`` (when it carries a 64-bit
+  significand) or exact ``fractions.Fraction``; each value ``v`` comes with
+  a magnitude ``M`` = the same expression with every term replaced by its
+  absolute value;
+* acceptance: ``|got_i - v_i| <= (L_i + 48) * 2^-53 * M_i`` element-wise
+  (L_i = products summed into element i), propagated bounds for reduced
+  scalars, bitwise equality where the result is exactly representable;
+* the shared inputs and runners: the same ``case`` objects and the same
+  ``run_*`` drivers serve the CPU tests (torch_ref, mutants) and the GPU
+  tests (gpu_ops), so the CPU discrimination check speaks about exactly the
+  inputs the kernels see.
+
+Why the bound holds.  A length-L recursive (or pairwise, or FMA) sum of
+products has running error <= L*u*sum|a_i b_i| (u = 2^-53, Higham 3.1; the
+quadratic term is below 1e-13 of that here).  The vector-update chain adds
+at most a handful of roundings on top, each relative to a partial result
+that is bounded by M.  The coefficients alpha/beta are themselves rounded:
+at most 4 operations, amplified by the cancellation factor of the
+pipelined alpha denominator, which the inputs keep <= 8 (asserted by
+:func:`pipe_expect`) -- 4*8 + the chain stays below the constant 48.
+"""
+
+from __future__ import annotations
+
+from fractions import Fraction
+from types import SimpleNamespace
+
+import numpy as np
+
+U = 2.0 ** -53
+EXTRA_OPS = 48
+C = 64
+MAXG = 16384
+USE_LONGDOUBLE = bool(np.finfo(np.longdouble).eps <= 2.0 ** -63)
+
+S_RR, S_PT, S_RR_PREV, S_BNRM2 = 0, 1, 2, 3
+S_GAMMA, S_DELTA, S_GAMMA_PREV, S_ALPHA_PREV = 4, 5, 6, 7
+S_NSLOTS = 8
+# distinct finite sentinels for scalar slots an operation must not touch
+SENTINELS = np.array([101.5, 102.25, 103.125, 104.75, 105.5, 106.25,
+                      107.125, 108.75])
+
+
+# ---------------------------------------------------------------------------
+# high-precision arithmetic
+
+def hps(x):
+    """fp64 scalar -> high-precision scalar (exact conversion)."""
+    return np.longdouble(x) if USE_LONGDOUBLE else Fraction(float(x))
+
+
+def hp(a):
+    """fp64 array -> high-precision array (exact conversion)."""
+    a = np.asarray(a, dtype=np.float64)
+    if USE_LONGDOUBLE:
+        return a.astype(np.longdouble)
+    out = np.empty(a.size, dtype=object)
+    for i, v in enumerate(a.ravel()):
+        out[i] = Fraction(float(v))
+    return out.reshape(a.shape)
+
+
+def hzeros(n):
+    return hp(np.zeros(n))
+
+
+def to_f64(a):
+    a = np.asarray(a)
+    if a.dtype == object:
+        return np.array([float(v) for v in a.ravel()]).reshape(a.shape)
+    return a.astype(np.float64)
+
+
+def habs(a):
+    return np.abs(a)
+
+
+def hsum(a):
+    s = hps(0.0)
+    return s + a.sum() if a.size else s
+
+
+def ratio_coeff(num, den):
+    """The kernels' safe_div in high precision: 0 when den == 0; a finite
+    numerator over an infinite denominator is exactly 0 in fp64 too."""
+    num, den = float(num), float(den)
+    if den == 0.0 or np.isinf(den):
+        return hps(0.0)
+    return hps(num) / hps(den)
+
+
+# ---------------------------------------------------------------------------
+# oracle operations: each returns (value, magnitude)
+
+def csr_rows(rowptr):
+    rowptr = np.asarray(rowptr, dtype=np.int64)
+    return np.repeat(np.arange(len(rowptr) - 1, dtype=np.int64), np.diff(rowptr))
+
+
+def spmv(rowptr, colidx, vals, x, xM=None):
+    """A x from the CSR.  ``x`` high-precision; ``xM`` its magnitude
+    (default |x|)."""
+    rows = csr_rows(rowptr)
+    cols = np.asarray(colidx, dtype=np.int64)
+    a = hp(vals)
+    n = len(rowptr) - 1
+    v, M = hzeros(n), hzeros(n)
+    np.add.at(v, rows, a * x[cols])
+    np.add.at(M, rows, habs(a) * (habs(x) if xM is None else xM)[cols])
+    return v, M
+
+
+def bound(M, L=0):
+    """Element-wise acceptance bound (L + 48) * 2^-53 * M."""
+    Lh = hp(np.broadcast_to(np.asarray(L, dtype=np.float64), np.shape(M)))
+    return (Lh + hps(float(EXTRA_OPS))) * hps(U) * M
+
+
+def dot(a, b, ta=None, tb=None, add=None):
+    """sum a_i b_i with the propagated tolerance of the issue:
+    sum(|a| tb + |b| ta + ta tb) + (n + 8) u sum|a b| (``add``: an old slot
+    value accumulated into; its magnitude joins the sum).
+    Returns (value, tolerance)."""
+    n = a.size
+    v = hsum(a * b)
+    M = hsum(habs(a) * habs(b))
+    tol = hps(0.0)
+    if ta is not None:
+        tol = tol + hsum(habs(b) * ta)
+    if tb is not None:
+        tol = tol + hsum(habs(a) * tb)
+    if ta is not None and tb is not None:
+        tol = tol + hsum(ta * tb)
+    if add is not None:
+        v = v + hps(add)
+        M = M + abs(hps(add))
+    return v, tol + hps(float(n + 8)) * hps(U) * M
+
+
+def sell_padded_len(rowptr, perm=None):
+    """Products per row in SELL-C-64: the slice's longest row.  ``perm``
+    (SELL row -> matrix row, sentinel nrows) for sigma-sorted structures."""
+    counts = np.diff(np.asarray(rowptr, dtype=np.int64))
+    nrows = len(counts)
+    nsl = (nrows + C - 1) // C
+    rowof = np.arange(nsl * C) if perm is None else np.asarray(perm, np.int64)
+    pad = np.zeros(nsl * C, dtype=np.int64)
+    ok = rowof < nrows
+    pad[ok] = counts[rowof[ok]]
+    smax = pad.reshape(nsl, C).max(axis=1)
+    L = np.zeros(nrows, dtype=np.int64)
+    L[rowof[ok]] = np.repeat(smax, C)[ok]
+    return L
+
+
+def bsell_padded_len(rowptr, colidx, dof):
+    """Products per scalar row in Block-SELL: dof * (most blocks of any node
+    in the 64-node slice)."""
+    rowptr = np.asarray(rowptr, dtype=np.int64)
+    nrows = len(rowptr) - 1
+    nnodes = nrows // dof
+    key = (csr_rows(rowptr) // dof) * (1 << 32) + np.asarray(colidx, np.int64) // dof
+    bnode = np.unique(key) >> 32
+    per_node = np.bincount(bnode, minlength=nnodes)
+    nsl = (nnodes + C - 1) // C
+    pad = np.zeros(nsl * C, dtype=np.int64)
+    pad[:nnodes] = per_node
+    smax = pad.reshape(nsl, C).max(axis=1)
+    return np.repeat(np.repeat(smax, C)[:nnodes], dof) * dof
+
+
+def unpack_bsell(bptr, bcol, bvals, nnodes, dof, ncols):
+    """Decode Block-SELL arrays into a dense (nnodes*dof, ncols) matrix.
+
+    Written from the layout comment above ``bval_off`` in kernels.hip, not
+    from the packer: per 64-node slice s (bptr in block units) the j-th
+    block of lane's node has block-column bcol[bptr[s] + j*64 + lane]; its
+    element k (row-major in the dof x dof block) sits at
+    bptr[s]*dof^2 + j*dof^2*64 + off, off = (k//2)*128 + lane*2 + (k&1) for
+    paired k and (dof^2-1)*64 + lane for the odd tail k = dof^2-1."""
+    bptr = np.asarray(bptr, dtype=np.int64)
+    bcol = np.asarray(bcol)
+    bvals = np.asarray(bvals, dtype=np.float64)
+    D2 = dof * dof
+    odd = D2 % 2 == 1
+    dense = np.zeros((nnodes * dof, ncols), dtype=np.float64)
+    for s in range(len(bptr) - 1):
+        assert (bptr[s + 1] - bptr[s]) % 64 == 0
+        blen = (bptr[s + 1] - bptr[s]) // 64
+        for j in range(blen):
+            for lane in range(64):
+                node = s * 64 + lane
+                cb = int(bcol[bptr[s] + j * 64 + lane])
+                assert 0 <= cb * dof and (cb + 1) * dof <= ncols, \
+                    "block column (padding included) must stay in bounds"
+                base = bptr[s] * D2 + j * D2 * 64
+                for k in range(D2):
+                    if odd and k == D2 - 1:
+                        off = (D2 - 1) * 64 + lane
+                    else:
+                        off = (k // 2) * 128 + lane * 2 + (k & 1)
+                    val = bvals[base + off]
+                    if node >= nnodes:
+                        assert val == 0.0, "padding lane holds a value"
+                        continue
+                    dense[node * dof + k // dof, cb * dof + k % dof] += val
+    return dense
+
+
+def csr_dense(rowptr, colidx, vals, ncols):
+    dense = np.zeros((len(rowptr) - 1, ncols), dtype=np.float64)
+    dense[csr_rows(rowptr), np.asarray(colidx, np.int64)] = vals
+    return dense
+
+
+# ---------------------------------------------------------------------------
+# acceptance
+
+class Expect:
+    """What one operation must produce: named arrays with element bounds,
+    named arrays that must match bitwise, and pairs of outputs that must be
+    bitwise equal to each other."""
+
+    def __init__(self, kernel):
+        self.kernel = kernel
+        self.close = {}
+        self.exact = {}
+        self.same = []
+
+    def add(self, name, v, M, L=0):
+        self.close[name] = (np.atleast_1d(v), np.atleast_1d(bound(np.atleast_1d(M), L)))
+
+    def add_tol(self, name, v, tol):
+        self.close[name] = (np.atleast_1d(v), np.atleast_1d(tol))
+
+    def add_exact(self, name, arr):
+        self.exact[name] = np.atleast_1d(np.asarray(arr, dtype=np.float64)).copy()
+
+    def add_same(self, a, b):
+        self.same.append((a, b))
+
+    def scalars(self, untouched_from, touched=()):
+        """Every slab slot not in ``touched`` must keep its input bits."""
+        for i in range(S_NSLOTS):
+            if i not in touched:
+                self.add_exact(f"scal{i}", untouched_from[i])
+
+
+def _bits_equal(a, b):
+    a = np.ascontiguousarray(np.atleast_1d(a), dtype=np.float64)
+    b = np.ascontiguousarray(np.atleast_1d(b), dtype=np.float64)
+    return a.shape == b.shape and bool(np.array_equal(a.view(np.int64), b.view(np.int64)))
+
+
+def ratios(expect, got):
+    """name -> worst error/bound (0 = exact, inf = NaN, a broken bitwise
+    check, or an error where the bound is 0)."""
+    out = {}
+    for name, (v, bnd) in expect.close.items():
+        g = np.atleast_1d(np.asarray(got[name], dtype=np.float64))
+        if g.shape != v.shape or not np.all(np.isfinite(g)):
+            out[name] = float("inf")
+            continue
+        if g.size == 0:
+            out[name] = 0.0
+            continue
+        err = habs(hp(g) - v)
+        zero = np.asarray(bnd == 0, dtype=bool)
+        safe = np.where(zero, hps(1.0), bnd)
+        r = to_f64(err / safe)
+        bad = zero & np.asarray(err != 0, dtype=bool)
+        r[zero] = 0.0
+        r[bad] = float("inf")
+        out[name] = float(r.max())
+    for name, want in expect.exact.items():
+        out[name] = 0.0 if _bits_equal(got[name], want) else float("inf")
+    for a, b in expect.same:
+        out[f"{a}=={b}"] = 0.0 if _bits_equal(got[a], got[b]) else float("inf")
+    return out
+
+
+def accepts(expect, got):
+    return all(r <= 1.0 for r in ratios(expect, got).values())
+
+
+def assert_accepts(expect, got, tag=""):
+    rs = ratios(expect, got)
+    worst = max((r for r in rs.values()), default=0.0)
+    print(f"ORACLE_RATIO kernel={expect.kernel} case={tag} worst={worst:.4g} "
+          + " ".join(f"{k}={v:.3g}" for k, v in rs.items() if v > 0))
+    bad = {k: v for k, v in rs.items() if not v <= 1.0}
+    assert not bad, f"{expect.kernel} [{tag}]: error/bound > 1 for {bad}"
+    return worst
+
+
+# ---------------------------------------------------------------------------
+# inputs
+
+_BASE_LENS = (0, 1, 7, 8, 9, 15, 16, 17)
+
+
+def rand_values(n, rng):
+    """Distinct fp64 values with |v| in [0.5, 2): no entry is small enough
+    to hide inside another entry's rounding error."""
+    v = rng.uniform(0.5, 2.0, size=n) * rng.choice([-1.0, 1.0], size=n)
+    assert len(np.unique(v)) == n
+    return v
+
+
+def ragged_counts(nrows, cap, rng):
+    """Row lengths such that every 64-row slice holds one long row (40..47,
+    cycling through every remainder mod 8) and rows of length
+    0, 1, 7, 8, 9, 15, 16, 17 (as far as the slice has rows); capped at the
+    number of columns."""
+    counts = rng.choice(_BASE_LENS, size=nrows)
+    for s0 in range(0, nrows, C):
+        hi = min(s0 + C, nrows)
+        counts[s0] = 40 + (3 * (s0 // C)) % 8
+        k = min(hi - s0 - 1, len(_BASE_LENS))
+        counts[s0 + 1:s0 + 1 + k] = _BASE_LENS[:k]
+    return np.minimum(counts, cap).astype(np.int64)
+
+
+def short_counts(nrows, rng):
+    """Slices whose LONGEST row has 0, 1, 7, 9, 0, ... entries: the SELL
+    kernels' main unrolled loop never runs (slice length < 8), runs exactly
+    once with a one-entry tail, or the slice is entirely empty."""
+    counts = np.zeros(nrows, dtype=np.int64)
+    for s0 in range(0, nrows, C):
+        hi = min(s0 + C, nrows)
+        top = (0, 1, 7, 9)[(s0 // C) % 4]
+        counts[s0:hi] = rng.integers(0, top + 1, size=hi - s0)
+        counts[s0 + (hi - s0) // 2] = top
+    return counts
+
+
+def csr_from_counts(counts, col_lo, col_hi, rng):
+    """Random CSR (sorted distinct columns in [col_lo, col_hi))."""
+    rowptr = np.zeros(len(counts) + 1, dtype=np.int64)
+    np.cumsum(counts, out=rowptr[1:])
+    cols = np.empty(int(rowptr[-1]), dtype=np.int64)
+    for i, c in enumerate(counts):
+        cols[rowptr[i]:rowptr[i + 1]] = col_lo + np.sort(
+            rng.choice(col_hi - col_lo, size=int(c), replace=False))
+    return rowptr, cols, rand_values(len(cols), rng)
+
+
+def sell_case(nslices, short=False):
+    rng = np.random.default_rng(1000 + nslices + (500 if short else 0))
+    nrows = nslices * C - 13
+    ncols = nrows + 37
+    counts = short_counts(nrows, rng) if short else ragged_counts(nrows, ncols, rng)
+    rowptr, cols, vals = csr_from_counts(counts, 0, ncols, rng)
+    return SimpleNamespace(nrows=nrows, ncols=ncols, rowptr=rowptr, cols=cols,
+                           vals=vals, x=rand_values(ncols, rng), nslices=nslices)
+
+
+def bsell_case(dof, nnodes, ghost, empty_slice=None):
+    """Block matrix with ragged block-rows, random unsymmetric blocks with
+    some off-diagonal entries missing, optional ghost block-columns and an
+    optional all-empty 64-node slice."""
+    rng = np.random.default_rng(2000 + 100 * dof + nnodes + (7 if ghost else 0)
+                                + (3 if empty_slice is not None else 0))
+    ncn = max(nnodes, 48) + 7 if ghost else nnodes
+    bcounts = ragged_counts(nnodes, ncn, rng)
+    if empty_slice is not None:
+        bcounts[empty_slice * C:(empty_slice + 1) * C] = 0
+    rows, cols = [], []
+    for nd in range(nnodes):
+        bcs = np.sort(rng.choice(ncn, size=int(bcounts[nd]), replace=False))
+        for a in range(dof):
+            for bc in bcs:
+                for b in range(dof):
+                    if a == b or rng.random() >= 0.25:
+                        rows.append(nd * dof + a)
+                        cols.append(bc * dof + b)
+    rows = np.asarray(rows, dtype=np.int64)
+    cols = np.asarray(cols, dtype=np.int64)
+    nrows = nnodes * dof
+    rowptr = np.zeros(nrows + 1, dtype=np.int64)
+    np.cumsum(np.bincount(rows, minlength=nrows), out=rowptr[1:])
+    vals = rand_values(len(cols), rng)
+    ncols = ncn * dof
+    return SimpleNamespace(dof=dof, nnodes=nnodes, nrows=nrows, ncols=ncols,
+                           rowptr=rowptr, cols=cols, vals=vals,
+                           x=rand_values(ncols, rng), pold=rand_values(ncols, rng),
+                           r=rand_values(ncols, rng))
+
+
+def pipe_case(nowned, split, nborder0=False, short=False):
+    """Local system of one rank: interior | border rows, owned | ghost
+    columns.  serial: no border, no ghosts.  ``nborder0``: ghosts exist but
+    no row couples to them (border_base = nowned, no matO pass).
+    ``short``: slice lengths 0/1/7/9 (see short_counts) in matA and matO."""
+    rng = np.random.default_rng(3000 + nowned + (1 if split else 0)
+                                + (2 if nborder0 else 0) + (500 if short else 0))
+    if split and not nborder0:
+        ninterior = {65: 37, 200: 131, 400: 150}.get(nowned, (nowned * 2) // 3 | 1)
+        assert ninterior % C
+    else:
+        ninterior = nowned
+    nborder = nowned - ninterior
+    nghost = 45 if split else 0
+    cntA = short_counts(nowned, rng) if short else ragged_counts(nowned, nowned, rng)
+    A = csr_from_counts(cntA, 0, nowned, rng)
+    if nborder:
+        cntO = short_counts(nborder, rng) if short else ragged_counts(nborder, nghost, rng)
+        O =csr_from_counts(cntO, nowned, nowned + nghost, rng)
+    else:
+        O = None
+    # the original local matrix: row-wise union (owned cols sort first)
+    cnt = cntA.copy()
+    if nborder:
+        cnt[ninterior:] += cntO
+    rowptr = np.zeros(nowned + 1, dtype=np.int64)
+    np.cumsum(cnt, out=rowptr[1:])
+    cols = np.empty(int(rowptr[-1]), dtype=np.int64)
+    vals = np.empty(int(rowptr[-1]))
+    for i in range(nowned):
+        a0, a1 = A[0][i], A[0][i + 1]
+        k = rowptr[i]
+        cols[k:k + a1 - a0] = A[1][a0:a1]
+        vals[k:k + a1 - a0] = A[2][a0:a1]
+        if i >= ninterior:
+            o0, o1 = O[0][i - ninterior], O[0][i - ninterior + 1]
+            cols[k + a1 - a0:rowptr[i + 1]] = O[1][o0:o1]
+            vals[k + a1 - a0:rowptr[i + 1]] = O[2][o0:o1]
+    vec = {k: rand_values(nowned, rng) for k in "ztpxr"}
+    scal = SENTINELS.copy()
+    scal[S_GAMMA], scal[S_DELTA] = 2.3719, 3.1427
+    scal[S_GAMMA_PREV], scal[S_ALPHA_PREV] = 1.7353, 2.9131
+    return SimpleNamespace(nowned=nowned, ninterior=ninterior, nborder=nborder,
+                           nghost=nghost, nlocal=nowned + nghost,
+                           border_base=ninterior if nborder else nowned,
+                           A=A, O=O, rowptr=rowptr, cols=cols, vals=vals,
+                           w_old=rand_values(nowned + nghost, rng), scal=scal,
+                           **vec)
+
+
+def vec_case(n, pt_zero=False):
+    rng = np.random.default_rng(4000 + n)
+    scal = SENTINELS.copy()
+    scal[S_RR] = 1.3719
+    scal[S_PT] = 0.0 if pt_zero else 2.9131
+    return SimpleNamespace(n=n, r=rand_values(n, rng), x=rand_values(n, rng),
+                           p=rand_values(n, rng), t=rand_values(n, rng),
+                           w=rand_values(n, rng),
+                           dinv=rng.uniform(0.5, 2.0, size=n), scal=scal)
+
+
+# ---------------------------------------------------------------------------
+# expectations
+
+def sell_blocks(nslices):
+    return (nslices * C + 255) // 256
+
+
+def elem_blocks(n):
+    return max(1, min(4096, (n + 1023) // 1024))
+
+
+def sell_spmv_expect(case, perm=None, dotslot=S_PT, dot_accum=False):
+    e = Expect("k_spmv_sell")
+    xh = hp(case.x)
+    y, M = spmv(case.rowptr, case.cols, case.vals, xh)
+    L = sell_padded_len(case.rowptr, perm)
+    e.add("y", y, M, L)
+    ty = bound(M, L)
+    d, tol = dot(xh[:case.nrows], y, tb=ty,
+                 add=SENTINELS[dotslot] if dot_accum else None)
+    e.add_tol(f"scal{dotslot}", d, tol)
+    e.scalars(SENTINELS, touched=(dotslot,))
+    return e
+
+
+def bsell_spmv_expect(case, dotslot=-1, dot_accum=False):
+    e = Expect("k_spmv_bsell")
+    xh = hp(case.x)
+    y, M = spmv(case.rowptr, case.cols, case.vals, xh)
+    L = bsell_padded_len(case.rowptr, case.cols, case.dof)
+    e.add("y", y, M, L)
+    if dotslot >= 0:
+        d, tol = dot(xh[:case.nrows], y, tb=bound(M, L),
+                     add=SENTINELS[dotslot] if dot_accum else None)
+        e.add_tol(f"scal{dotslot}", d, tol)
+    e.scalars(SENTINELS, touched=(dotslot,))
+    return e
+
+
+def bsell_daypx_scal(beta_zero):
+    scal = SENTINELS.copy()
+    scal[S_RR] = 1.3719
+    scal[S_RR_PREV] = np.inf if beta_zero else 2.9131
+    return scal
+
+
+def bsell_daypx_expect(case, beta_zero):
+    assert case.ncols == case.nrows
+    e = Expect("k_spmv_bsell_daypx")
+    scal = bsell_daypx_scal(beta_zero)
+    beta = ratio_coeff(scal[S_RR], scal[S_RR_PREV])
+    pn = beta * hp(case.pold) + hp(case.r)
+    Mp = abs(beta) * habs(hp(case.pold)) + habs(hp(case.r))
+    if beta_zero:
+        e.add_exact("pnew", case.r)
+    else:
+        e.add("pnew", pn, Mp)
+    y, My = spmv(case.rowptr, case.cols, case.vals, pn, xM=Mp)
+    L = bsell_padded_len(case.rowptr, case.cols, case.dof)
+    e.add("y", y, My, L)
+    d, tol = dot(pn, y, ta=bound(Mp), tb=bound(My, L))
+    e.add_tol(f"scal{S_PT}", d, tol)
+    e.scalars(scal, touched=(S_PT,))
+    return e
+
+
+def pipe_coeffs(scal, first):
+    """(beta, alpha, cancellation factor of alpha's denominator)."""
+    if first:
+        return hps(0.0), ratio_coeff(scal[S_GAMMA], scal[S_DELTA]), 1.0
+    beta = ratio_coeff(scal[S_GAMMA], scal[S_GAMMA_PREV])
+    sub = beta * ratio_coeff(scal[S_GAMMA], scal[S_ALPHA_PREV])
+    den = hps(scal[S_DELTA]) - sub
+    kappa = float((abs(hps(scal[S_DELTA])) + abs(sub)) / abs(den))
+    return beta, hps(scal[S_GAMMA]) / den, kappa
+
+
+def pipe_expect(case, first):
+    """One full megafused iteration (all passes + finalize)."""
+    e = Expect("k_sell_pipe")
+    n = case.nowned
+    w = hp(case.w_old)
+    q, Mq = spmv(case.rowptr, case.cols, case.vals, w)
+    L = sell_padded_len(case.A[0])
+    if case.nborder:
+        L[case.ninterior:] += sell_padded_len(case.O[0])
+    _pipelined_update(e, case, first, q, Mq, L, w[:n], "w_new")
+    if case.nghost:
+        e.add_exact("w_new_tail", np.full(case.nghost, np.nan))
+    if case.nborder:  # the matA pass alone must leave the border rows alone
+        for k in "ztpxr":
+            e.add_exact(f"matA/{k}_border", getattr(case, k)[case.ninterior:])
+        e.add_exact("matA/w_new_border", np.full(case.nborder + case.nghost, np.nan))
+    return e
+
+
+def _pipelined_update(e, case, first, q, Mq, L, wo, wname):
+    """Ghysels-Vanroose 6-vector update + next gamma/delta + rotation, given
+    q = A w with magnitude Mq built from L products per element."""
+    beta, alpha, kappa = pipe_coeffs(case.scal, first)
+    assert kappa <= 8.0, f"alpha denominator cancels too much: {kappa}"
+    ab, aa = abs(beta), abs(alpha)
+    z0, t0, p0, x0, r0 = (hp(getattr(case, k)) for k in "ztpxr")
+    z, Mz = q + beta * z0, Mq + ab * habs(z0)
+    t, Mt = wo + beta * t0, habs(wo) + ab * habs(t0)
+    p, Mp = r0 + beta * p0, habs(r0) + ab * habs(p0)
+    x, Mx = x0 + alpha * p, habs(x0) + aa * Mp
+    r, Mr = r0 - alpha * t, habs(r0) + aa * Mt
+    wn, Mw = wo - alpha * z, habs(wo) + aa * Mz
+    e.add("z", z, Mz, L)
+    e.add("t", t, Mt)
+    e.add("p", p, Mp)
+    e.add("x", x, Mx)
+    e.add("r", r, Mr)
+    e.add(wname, wn, Mw, L)
+    g, gtol = dot(r, r, ta=bound(Mr), tb=bound(Mr))
+    d, dtol = dot(wn, r, ta=bound(Mw, L), tb=bound(Mr))
+    e.add_exact(f"scal{S_GAMMA_PREV}", case.scal[S_GAMMA])
+    e.add(f"scal{S_ALPHA_PREV}", alpha, aa)
+    e.add_tol(f"scal{S_GAMMA}", g, gtol)
+    e.add_tol(f"scal{S_DELTA}", d, dtol)
+    e.scalars(case.scal, touched=(S_GAMMA, S_DELTA, S_GAMMA_PREV, S_ALPHA_PREV))
+
+
+def fused_case(n):
+    """Inputs of the unfused pipelined update: q is a plain input vector."""
+    rng = np.random.default_rng(5000 + n)
+    scal = SENTINELS.copy()
+    scal[S_GAMMA], scal[S_DELTA] = 2.3719, 3.1427
+    scal[S_GAMMA_PREV], scal[S_ALPHA_PREV] = 1.7353, 2.9131
+    return SimpleNamespace(n=n, scal=scal,
+                           **{k: rand_values(n, rng) for k in "ztpxrwq"})
+
+
+def fused_expect(case, first):
+    e = Expect("k_pipelined_fused")
+    q = hp(case.q)
+    _pipelined_update(e, case, first, q, habs(q), 0, hp(case.w), "w")
+    return e
+
+
+def run_fused(ops, case, dev, first, **kw):
+    v = {k: _t(getattr(case, k), dev) for k in "ztpxrwq"}
+    scal = _t(case.scal, dev)
+    partials = _nan(2 * MAXG, dev)
+    ops.pipelined_fused(v["z"], v["t"], v["p"], v["x"], v["r"], v["w"], v["q"],
+                        scal, partials, case.n, first, **kw)
+    got = {k: _np(v[k]) for k in "ztpxrw"}
+    _partials_out(got, partials, elem_blocks(case.n))
+    return _scal_out(got, scal)
+
+
+def csr_blocks(nrows, lanes):
+    return min(MAXG, (nrows + 256 // lanes - 1) // (256 // lanes))
+
+
+def csr_spmv_expect(case, rowbase=0, accum=False, dot_accum=False,
+                    kernel="spmv_csr_vector"):
+    """CSR SpMV into y[rowbase:rowbase+nrows] of a buffer with ``rowbase``
+    extra rows on either side; ``accum`` adds to y0 = case.x[:nrows]
+    reversed (any known finite vector does)."""
+    e = Expect(kernel)
+    xh = hp(case.x)
+    c, M = spmv(case.rowptr, case.cols, case.vals, xh)
+    L = np.diff(case.rowptr)
+    y, My = c, M
+    if accum:
+        y0 = hp(csr_y0(case))
+        y, My = y0 + c, habs(y0) + M
+    e.add("y", y, My, L)
+    e.add_exact("y_outside", np.full(2 * rowbase, np.nan))
+    d, tol = dot(xh[rowbase:rowbase + case.nrows], c, tb=bound(M, L),
+                 add=SENTINELS[S_PT] if dot_accum else None)
+    e.add_tol(f"scal{S_PT}", d, tol)
+    e.scalars(SENTINELS, touched=(S_PT,))
+    return e
+
+
+def csr_y0(case):
+    return case.x[:case.nrows][::-1].copy()
+
+
+def run_csr_spmv(ops, case, dev, *, rowbase=0, accum=False, dot_accum=False,
+                 col64=False, lanes=None, binned=False):
+    n = case.nrows
+    y = _nan(n + 2 * rowbase, dev)
+    if accum:
+        y[rowbase:rowbase + n] = _t(csr_y0(case), dev)
+    scal = _t(SENTINELS, dev)
+    partials = _nan(2 * MAXG, dev)
+    cols = _t(case.cols.astype(np.int64 if col64 else np.int32), dev)
+    kw = dict(rowbase=rowbase, accum=accum, partials=partials, scal=scal,
+              dotslot=S_PT, dot_accum=dot_accum)
+    if binned:
+        from acg_amd.ops.gpu_ops import build_row_bins  # host-side numpy prep
+
+        rowlist, bins = build_row_bins(case.rowptr)
+        ops.spmv_binned(_t(case.rowptr, dev), cols, _t(case.vals, dev),
+                        _t(rowlist, dev), bins, _t(case.x, dev), y, **kw)
+        nb = sum(csr_blocks(cnt, ln) for _, cnt, ln in bins)
+    else:
+        if lanes is not None:
+            kw["lanes"] = lanes
+        ops.spmv(_t(case.rowptr, dev), cols, _t(case.vals, dev),
+                 _t(case.x, dev), y, **kw)
+        nb = csr_blocks(n, lanes or 16)
+    yy = _np(y)
+    got = {"y": yy[rowbase:rowbase + n],
+           "y_outside": np.concatenate([yy[:rowbase], yy[rowbase + n:]])}
+    _partials_out(got, partials, nb)
+    return _scal_out(got, scal)
+
+
+def ratio_update_expect(case, op, n_act):
+    """axpy_ratio (y += sign*(num/den)*x, sign = -1) or daypx_ratio
+    (y = (num/den)*y + x) on the first n_act elements; num/den =
+    scal[S_RR]/scal[S_PT]."""
+    e = Expect(f"k_{op}")
+    a = ratio_coeff(case.scal[S_RR], case.scal[S_PT])
+    y0, x0 = hp(case.r[:n_act]), hp(case.x[:n_act])
+    if op == "axpy_ratio":
+        e.add("y", y0 - a * x0, habs(y0) + abs(a) * habs(x0))
+    else:
+        e.add("y", a * y0 + x0, abs(a) * habs(y0) + habs(x0))
+    e.add_exact("y_tail", case.r[n_act:])
+    e.scalars(case.scal)
+    return e
+
+
+def run_ratio_update(ops, case, dev, op, n_act):
+    y, scal = _t(case.r, dev), _t(case.scal, dev)
+    if op == "axpy_ratio":
+        ops.axpy_ratio(y, _t(case.x, dev), scal, S_RR, S_PT, sign=-1.0, n=n_act)
+    else:
+        ops.daypx_ratio(y, _t(case.x, dev), scal, S_RR, S_PT, n=n_act)
+    yy = _np(y)
+    return _scal_out({"y": yy[:n_act], "y_tail": yy[n_act:]}, scal)
+
+
+def run_exact_ops(ops, dev, idx64):
+    """pack_gather, zero_scalars, cg_prep_pt, cg_prep_rr: pure data movement,
+    every result is bitwise defined.  Returns (expect, got)."""
+    rng = np.random.default_rng(6000)
+    e, got = Expect("k_pack_gather/k_zero_scalars/k_cg_prep"), {}
+    x = rand_values(1500, rng)
+    idx = rng.integers(0, 1500, size=777).astype(np.int64 if idx64 else np.int32)
+    send = _nan(777 + 5, dev)
+    ops.pack_gather(send[:777], _t(x, dev), _t(idx, dev))
+    e.add_exact("sendbuf", np.concatenate([x[idx], np.full(5, np.nan)]))
+    got["sendbuf"] = _np(send)
+    want = SENTINELS.copy()
+    want[2:5] = 0.0
+    scal = _t(SENTINELS, dev)
+    ops.zero_scalars(scal, 2, 3)
+    e.add_exact("zeroed", want)
+    got["zeroed"] = _np(scal)
+    scal = _t(SENTINELS, dev)
+    ops.cg_prep_pt(scal)
+    ops.cg_prep_rr(scal)
+    want = SENTINELS.copy()
+    want[S_PT], want[S_RR_PREV] = 0.0, SENTINELS[S_RR]
+    e.add_exact("prepped", want)
+    got["prepped"] = _np(scal)
+    return e, got
+
+
+def pcg_expect(case):
+    e = Expect("k_pcg_fused_update")
+    alpha = ratio_coeff(case.scal[S_RR], case.scal[S_PT])
+    aa = abs(alpha)
+    r0, x0, p0, t0 = (hp(getattr(case, k)) for k in "rxpt")
+    dinv = hp(case.dinv)
+    r, Mr = r0 - alpha * t0, habs(r0) + aa * habs(t0)
+    x, Mx = x0 + alpha * p0, habs(x0) + aa * habs(p0)
+    z, Mz = dinv * r, dinv * Mr
+    if float(case.scal[S_PT]) == 0.0:
+        e.add_exact("r", case.r)
+        e.add_exact("x", case.x)
+    else:
+        e.add("r", r, Mr)
+        e.add("x", x, Mx)
+    e.add("z", z, Mz)
+    e.add_same("z", "dinv*r")
+    rz, rztol = dot(r, z, ta=bound(Mr), tb=bound(Mz))
+    rr, rrtol = dot(r, r, ta=bound(Mr), tb=bound(Mr))
+    e.add_exact(f"scal{S_RR_PREV}", case.scal[S_RR])
+    e.add_tol(f"scal{S_RR}", rz, rztol)
+    e.add_tol(f"scal{S_GAMMA}", rr, rrtol)
+    e.scalars(case.scal, touched=(S_RR, S_RR_PREV, S_GAMMA))
+    return e
+
+
+def cg_update_expect(case):
+    e = Expect("k_cg_fused_update")
+    alpha = ratio_coeff(case.scal[S_RR], case.scal[S_PT])
+    aa = abs(alpha)
+    r0, x0, p0, t0 = (hp(getattr(case, k)) for k in "rxpt")
+    r, Mr = r0 - alpha * t0, habs(r0) + aa * habs(t0)
+    x, Mx = x0 + alpha * p0, habs(x0) + aa * habs(p0)
+    e.add("r", r, Mr)
+    e.add("x", x, Mx)
+    rr, rrtol = dot(r, r, ta=bound(Mr), tb=bound(Mr))
+    e.add_exact(f"scal{S_RR_PREV}", case.scal[S_RR])
+    e.add_tol(f"scal{S_RR}", rr, rrtol)
+    e.scalars(case.scal, touched=(S_RR, S_RR_PREV))
+    return e
+
+
+def dot_expect(case, slot, accumulate):
+    e = Expect("k_dot")
+    d, tol = dot(hp(case.r), hp(case.w),
+                 add=SENTINELS[slot] if accumulate else None)
+    e.add_tol(f"scal{slot}", d, tol)
+    e.scalars(SENTINELS, touched=(slot,))
+    return e
+
+
+def dot2_expect(case, accumulate):
+    e = Expect("k_dot2")
+    g, gtol = dot(hp(case.r), hp(case.r),
+                  add=SENTINELS[S_GAMMA] if accumulate else None)
+    d, dtol = dot(hp(case.w), hp(case.r),
+                  add=SENTINELS[S_DELTA] if accumulate else None)
+    e.add_tol(f"scal{S_GAMMA}", g, gtol)
+    e.add_tol(f"scal{S_DELTA}", d, dtol)
+    e.scalars(SENTINELS, touched=(S_GAMMA, S_DELTA))
+    return e
+
+
+# ---------------------------------------------------------------------------
+# runners: drive ``ops`` (torch_ref or gpu_ops) on poisoned buffers and
+# collect everything the expectations name
+
+def _t(a, dev):
+    import torch
+
+    return torch.from_numpy(np.array(a, copy=True, order="C")).to(dev)  # never alias the case
+
+
+def _nan(n, dev):
+    import torch
+
+    return torch.full((n,), float("nan"), dtype=torch.float64, device=dev)
+
+
+def _np(t):
+    return t.detach().cpu().numpy().copy()
+
+
+def _scal_out(got, scal):
+    s = _np(scal)
+    for i in range(S_NSLOTS):
+        got[f"scal{i}"] = s[i:i + 1]
+    return got
+
+
+def _partials_out(got, partials, nblocks):
+    got["partials"] = _np(partials)
+    got["nblocks"] = int(nblocks)
+    return got
+
+
+def run_sell_spmv(ops, case, dev, *, col64=False, variant=None, sigma=1,
+                  dotslot=S_PT, dot_accum=False, packed=None):
+    from acg_amd.ops import torch_ref
+
+    if packed is None:
+        packed = torch_ref.sell_from_csr(
+            case.rowptr, case.cols.astype(np.int64 if col64 else np.int32),
+            case.vals, sigma=sigma)
+    sp, sc, sv = packed[:3]
+    kw = {}
+    if len(packed) == 4:
+        kw["perm"] = _t(packed[3], dev)
+    if variant is not None:
+        kw["variant"] = variant
+    y = _nan(case.nrows, dev)
+    scal = _t(SENTINELS, dev)
+    partials = _nan(2 * MAXG, dev)
+    ops.spmv_sell(_t(sp, dev), _t(sc, dev), _t(sv, dev), case.nrows,
+                  _t(case.x, dev), y, partials=partials, scal=scal,
+                  dotslot=dotslot, dot_accum=dot_accum, **kw)
+    got = {"y": _np(y)}
+    _partials_out(got, partials, sell_blocks(case.nslices))
+    return _scal_out(got, scal)
+
+
+def pack_bsell(case, dev):
+    from acg_amd.ops import torch_ref
+
+    bptr, bcol, bvals, _ = torch_ref.bsell_from_csr(case.rowptr, case.cols,
+                                                    case.vals, case.dof)
+    return _t(bptr, dev), _t(bcol, dev), _t(bvals, dev)
+
+
+def run_bsell_spmv(ops, case, dev, *, dotslot=-1, dot_accum=False, packed=None):
+    bptr, bcol, bvals = packed if packed is not None else pack_bsell(case, dev)
+    y = _nan(case.nrows, dev)
+    scal = _t(SENTINELS, dev)
+    partials = _nan(2 * MAXG, dev)
+    kw = dict(partials=partials, scal=scal, dotslot=dotslot,
+              dot_accum=dot_accum) if dotslot >= 0 else {}
+    ops.spmv_bsell(bptr, bcol, bvals, case.nnodes, case.dof, _t(case.x, dev),
+                   y, **kw)
+    got = {"y": _np(y)}
+    _partials_out(got, partials, sell_blocks(bptr.numel() - 1) if dotslot >= 0 else 0)
+    return _scal_out(got, scal)
+
+
+def run_bsell_daypx(ops, case, dev, beta_zero, packed=None):
+    bptr, bcol, bvals = packed if packed is not None else pack_bsell(case, dev)
+    y, pnew = _nan(case.nrows, dev), _nan(case.nrows, dev)
+    scal = _t(bsell_daypx_scal(beta_zero), dev)
+    partials = _nan(2 * MAXG, dev)
+    ops.spmv_bsell_daypx(bptr, bcol, bvals, case.nnodes, case.dof,
+                         _t(case.pold, dev), _t(case.r, dev), pnew, y, scal,
+                         partials, S_PT)
+    got = {"y": _np(y), "pnew": _np(pnew)}
+    _partials_out(got, partials, sell_blocks(bptr.numel() - 1))
+    return _scal_out(got, scal)
+
+
+def run_pipe(ops, case, dev, first):
+    """matA pass, (matO pass with partials_off = nbA,) finalize."""
+    from acg_amd.ops import torch_ref
+
+    n = case.nowned
+
+    def pack(csr):
+        sp, sc, sv = torch_ref.sell_from_csr(csr[0], csr[1].astype(np.int32), csr[2])
+        return _t(sp, dev), _t(sc, dev), _t(sv, dev)
+
+    v = {k: _t(getattr(case, k), dev) for k in "ztpxr"}
+    w_old = _t(case.w_old, dev)
+    w_new = _nan(case.nlocal, dev)
+    qpart = _nan(max(case.nborder, 1), dev)
+    scal = _t(case.scal, dev)
+    partials = _nan(2 * MAXG, dev)
+    nb = ops.sell_pipe(*pack(case.A), n, 0, case.border_base, w_old, qpart,
+                       v["z"], v["t"], v["p"], v["x"], v["r"], w_new, scal,
+                       first, partials, 0, mato=False)
+    got = {}
+    if case.nborder:
+        for k in "ztpxr":
+            got[f"matA/{k}_border"] = _np(v[k][case.ninterior:])
+        got["matA/w_new_border"] = _np(w_new[case.ninterior:])
+        nb += ops.sell_pipe(*pack(case.O), case.nborder, case.ninterior,
+                            case.ninterior, w_old, qpart, v["z"], v["t"],
+                            v["p"], v["x"], v["r"], w_new, scal, first,
+                            partials, nb, mato=True)
+    ops.pipelined_finalize(partials, nb, scal, first)
+    for k in "ztpxr":
+        got[k] = _np(v[k])
+    got["w_new"] = _np(w_new[:n])
+    got["w_new_tail"] = _np(w_new[n:])
+    _partials_out(got, partials, nb)
+    return _scal_out(got, scal)
+
+
+def run_pcg(ops, case, dev):
+    r, x, z = _t(case.r, dev), _t(case.x, dev), _nan(case.n, dev)
+    scal = _t(case.scal, dev)
+    partials = _nan(2 * MAXG, dev)
+    ops.pcg_fused_update(r, x, _t(case.p, dev), _t(case.t, dev), z,
+                         _t(case.dinv, dev), scal, partials, case.n)
+    got = {"r": _np(r), "x": _np(x), "z": _np(z)}
+    got["dinv*r"] = case.dinv * got["r"]
+    _partials_out(got, partials, elem_blocks(case.n))
+    return _scal_out(got, scal)
+
+
+def run_cg_update(ops, case, dev):
+    r, x = _t(case.r, dev), _t(case.x, dev)
+    scal = _t(case.scal, dev)
+    partials = _nan(2 * MAXG, dev)
+    ops.cg_fused_update(r, x, _t(case.p, dev), _t(case.t, dev), scal,
+                        partials, case.n)
+    got = {"r": _np(r), "x": _np(x)}
+    _partials_out(got, partials, elem_blocks(case.n))
+    return _scal_out(got, scal)
+
+
+def run_dot(ops, case, dev, slot, accumulate):
+    scal = _t(SENTINELS, dev)
+    partials = _nan(2 * MAXG, dev)
+    ops.dot(_t(case.r, dev), _t(case.w, dev), partials, scal, slot,
+            accumulate=accumulate)
+    return _scal_out(_partials_out({}, partials, elem_blocks(case.n)), scal)
+
+
+def run_dot2(ops, case, dev, accumulate):
+    scal = _t(SENTINELS, dev)
+    partials = _nan(2 * MAXG, dev)
+    ops.dot2(_t(case.r, dev), _t(case.w, dev), partials, scal, case.n,
+             accumulate=accumulate)
+    return _scal_out(_partials_out({}, partials, elem_blocks(case.n)), scal)
+
+
+def check_partials(got, halves):
+    """GPU only: slots >= nblocks keep their NaN prefill bits in both halves
+    of the scratch; the slots the launch owns hold finite sums."""
+    part, nb = got["partials"], got["nblocks"]
+    nanbits = np.array([np.nan]).view(np.int64)[0]
+    bits = part.view(np.int64)
+    assert np.all(bits[nb:MAXG] == nanbits), "partials beyond nblocks written"
+    lo = MAXG + (nb if halves == 2 else 0)
+    assert np.all(bits[lo:] == nanbits), "second-half partials written"
+    assert np.all(np.isfinite(part[:nb]))
+    if halves == 2:
+        assert np.all(np.isfinite(part[MAXG:MAXG + nb]))

@@ -1,5 +1,7 @@
-"""GPU kernel numerics: every gfx950 HIP kernel vs the plain-torch fp64
-reference (ops.torch_ref), per the test strategy in SURVEY.md §4."""
+"""GPU kernel numerics: gfx950 HIP kernels vs the plain-torch fp64
+reference (ops.torch_ref), per the test strategy in SURVEY.md §4.  The
+element-wise exactness checks with derived bounds (block-SELL, megafused,
+PCG, SELL variants, reductions) live in test_gpu_kernel_oracle.py."""
 
 import numpy as np
 import pytest

@@ -7,8 +7,9 @@ Mirrors the reference option surface (acg-hip.c:312-374) and its pipeline
 write solution to stdout.  Multi-rank runs come from torchrun (one process
 per GPU, RCCL) instead of mpirun; --comm gloo supports CPU multi-process.
 
-Solvers: acg (GPU classic CG), acg-pipelined (GPU pipelined),
-cpu / cpu-pipelined (host torch), scipy / scipy-pipelined (independent
+Solvers: acg (GPU classic CG), acg-pipelined (GPU pipelined), acg-mixed /
+cpu-mixed (fp32-stored operator + fp64 refinement), cpu / cpu-pipelined
+(host torch), scipy / scipy-pipelined (independent
 oracle, the role PETSc KSPCG plays in the reference -- PETSc is not in
 this image).
 """
@@ -48,8 +49,9 @@ def make_parser() -> argparse.ArgumentParser:
     p.add_argument("--seed", type=int, default=0, help="partitioner seed")
     p.add_argument("--solver", default=None,
                    choices=("acg", "acg-pipelined", "acg-device",
-                            "acg-jacobi", "cpu", "cpu-pipelined",
-                            "cpu-jacobi", "scipy", "scipy-pipelined",
+                            "acg-jacobi", "acg-mixed", "cpu", "cpu-pipelined",
+                            "cpu-jacobi", "cpu-mixed", "scipy",
+                            "scipy-pipelined",
                             "petsc", "petsc-pipelined"),
                    help="default: acg on GPU, cpu otherwise.  petsc[-pipelined] "
                         "are accepted for aCG compatibility and run the scipy "
@@ -59,6 +61,10 @@ def make_parser() -> argparse.ArgumentParser:
     p.add_argument("--diff-rtol", type=float, default=0.0)
     p.add_argument("--residual-atol", type=float, default=0.0)
     p.add_argument("--residual-rtol", type=float, default=1e-9)
+    p.add_argument("--inner-rtol", type=float, default=None,
+                   help="acg-mixed / cpu-mixed: relative residual reduction "
+                        "of each fp32-operator sweep between fp64 "
+                        "refinement steps (default: the solver's)")
     p.add_argument("--epsilon", type=float, default=0.0,
                    help="diagonal shift added to A")
     p.add_argument("--warmup", type=int, default=10,
@@ -302,6 +308,8 @@ def main(argv=None) -> int:
             b = b.to(device)
             x = x.to(device)
             diff_requested = args.diff_atol > 0 or args.diff_rtol > 0
+            mixed_kw = ({} if args.inner_rtol is None
+                        else {"inner_rtol": args.inner_rtol})
             if diff_requested and solver_name != "acg":
                 # reference parity: the GPU pipelined/device solvers REJECT
                 # diff tolerances (cghip.c:427, 1212) rather than silently
@@ -317,6 +325,9 @@ def main(argv=None) -> int:
                 elif solver_name == "acg-jacobi":
                     solver.solve_jacobi(b, x.clone(), maxits=args.warmup,
                                         res_rtol=0.0)
+                elif solver_name == "acg-mixed":
+                    solver.solve_mixed(b, x.clone(), maxits=args.warmup,
+                                       res_rtol=0.0, **mixed_kw)
                 elif solver_name == "acg-device":
                     # warm the actual cooperative kernel (reference warms the
                     # kernel it will time, cg-kernels-hip.hip:1925-1989)
@@ -332,6 +343,11 @@ def main(argv=None) -> int:
                 res = solver.solve_jacobi(b, x, maxits=args.max_iterations,
                                           res_atol=args.residual_atol,
                                           res_rtol=args.residual_rtol)
+            elif solver_name == "acg-mixed":
+                res = solver.solve_mixed(b, x, maxits=args.max_iterations,
+                                         res_atol=args.residual_atol,
+                                         res_rtol=args.residual_rtol,
+                                         **mixed_kw)
             elif solver_name == "acg-device":
                 res = solver.solve_device(b, x, maxits=args.max_iterations,
                                           res_atol=args.residual_atol,
@@ -354,6 +370,16 @@ def main(argv=None) -> int:
                 res = solver.solve_jacobi(b, x, maxits=args.max_iterations,
                                           res_atol=args.residual_atol,
                                           res_rtol=args.residual_rtol)
+            elif solver_name == "cpu-mixed":
+                if args.diff_atol > 0 or args.diff_rtol > 0:
+                    raise AcgError(ErrCode.NOT_SUPPORTED,
+                                   "--diff-atol/--diff-rtol are not supported "
+                                   "by cpu-mixed (use acg or cpu)")
+                res = solver.solve_mixed(
+                    b, x, maxits=args.max_iterations,
+                    res_atol=args.residual_atol, res_rtol=args.residual_rtol,
+                    **({} if args.inner_rtol is None
+                       else {"inner_rtol": args.inner_rtol}))
             else:
                 res = solver.solve(b, x, maxits=args.max_iterations,
                                    res_atol=args.residual_atol,

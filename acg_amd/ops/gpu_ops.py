@@ -180,6 +180,20 @@ SELL_NT, SELL_SWZ, SELL_U8 = 1, 2, 4
 # negative (x is L3-resident, natural slice order already L2-local).
 DEFAULT_SELL_VARIANT = SELL_NT | SELL_U8
 
+# Storage types the SELL / BSELL operator values may have.  fp32 values
+# keep the fp64 element order (``vals.to(torch.float32)`` is the pack
+# step); the kernels widen them on load and compute in fp64.
+OPERATOR_VALUE_DTYPES = (torch.float64, torch.float32)
+
+
+def _val32(vals: torch.Tensor, what: str) -> bool:
+    """True for fp32-stored values; TypeError (before any launch) for a
+    dtype the kernels would misread."""
+    if vals.dtype not in OPERATOR_VALUE_DTYPES:
+        raise TypeError(f"{what}: operator values must be float64 or "
+                        f"float32, got {vals.dtype}")
+    return vals.dtype == torch.float32
+
 
 def spmv_sell(sellptr: torch.Tensor, cols: torch.Tensor, vals: torch.Tensor,
               nrows: int, x: torch.Tensor, y: torch.Tensor, *,
@@ -189,19 +203,26 @@ def spmv_sell(sellptr: torch.Tensor, cols: torch.Tensor, vals: torch.Tensor,
               dot_accum: bool = True, variant: int | None = None,
               perm: torch.Tensor | None = None) -> None:
     """SELL-C-64(-sigma) SpMV.  ``perm`` (int32) maps SELL row -> matrix
-    row for sigma-sorted irregular matrices."""
+    row for sigma-sorted irregular matrices.  ``vals`` may be stored in
+    fp32 (see OPERATOR_VALUE_DTYPES); only the default ``variant`` exists
+    for fp32 values."""
+    if variant is None:
+        variant = DEFAULT_SELL_VARIANT
+    val32 = _val32(vals, "spmv_sell")
+    if val32 and (variant & (SELL_NT | SELL_SWZ | SELL_U8)) != DEFAULT_SELL_VARIANT:
+        raise TypeError("spmv_sell: float32 values support only the default "
+                        f"variant {DEFAULT_SELL_VARIANT}, got {variant}")
     nslices = sellptr.numel() - 1
     if nslices <= 0:
         return
-    if variant is None:
-        variant = DEFAULT_SELL_VARIANT
     fuse = scal is not None and dotslot >= 0
     K.spmv_sell(nslices, nrows, rowbase, sellptr.data_ptr(), cols.data_ptr(),
                 1 if cols.dtype == torch.int64 else 0,
                 vals.data_ptr(), x.data_ptr(), y.data_ptr(), accum,
                 partials.data_ptr() if fuse else 0,
                 scal.data_ptr() if fuse else 0, dotslot, dot_accum,
-                variant, perm.data_ptr() if perm is not None else 0, _stream())
+                variant, perm.data_ptr() if perm is not None else 0, val32,
+                _stream())
 
 
 def spmv_bsell(bptr: torch.Tensor, bcol: torch.Tensor, bvals: torch.Tensor,
@@ -209,7 +230,9 @@ def spmv_bsell(bptr: torch.Tensor, bcol: torch.Tensor, bvals: torch.Tensor,
                partials: torch.Tensor | None = None,
                scal: torch.Tensor | None = None, dotslot: int = -1,
                dot_accum: bool = True) -> None:
-    """Block-SELL SpMV (dense dof x dof blocks; one int32 index per block)."""
+    """Block-SELL SpMV (dense dof x dof blocks; one int32 index per block).
+    ``bvals`` may be stored in fp32 (see OPERATOR_VALUE_DTYPES)."""
+    val32 = _val32(bvals, "spmv_bsell")
     nslices = bptr.numel() - 1
     if nslices <= 0:
         return
@@ -217,7 +240,8 @@ def spmv_bsell(bptr: torch.Tensor, bcol: torch.Tensor, bvals: torch.Tensor,
     K.spmv_bsell(nslices, nnodes, dof, bptr.data_ptr(), bcol.data_ptr(),
                  bvals.data_ptr(), x.data_ptr(), y.data_ptr(),
                  partials.data_ptr() if fuse else 0,
-                 scal.data_ptr() if fuse else 0, dotslot, dot_accum, _stream())
+                 scal.data_ptr() if fuse else 0, dotslot, dot_accum, val32,
+                 _stream())
 
 
 def stencil_spmv(mf, nrows_nodes: int, row0_node: int, x: torch.Tensor,

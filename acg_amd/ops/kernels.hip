@@ -173,13 +173,17 @@ spmv_csr_vector(long nrows, long rowbase,
 template <typename T>
 __device__ __forceinline__ T ld_nt(const T* p) { return __builtin_nontemporal_load(p); }
 
+// ValT: storage type of the operator values, double or float.  fp32-stored
+// values keep the same element order (vals.to(float32) is the whole pack
+// step) and are widened to fp64 on load, which is exact; x, products, row
+// sums, y and the fused dot stay fp64.  Matrix stream 12 -> 8 B per entry.
 template <typename ColT, bool ACCUM, bool FUSE_DOT, bool NT, bool SWZ, int UNROLL,
-          bool PERM = false>
+          bool PERM = false, typename ValT = double>
 __global__ void __launch_bounds__(BLOCK)
 k_spmv_sell(long nslices, long nrows, long rowbase,
           const long* __restrict__ sellptr,   // [nslices+1], element offsets
           const ColT* __restrict__ cols,      // padded entries: col of pad = row
-          const double* __restrict__ vals,    // pad value = 0
+          const ValT* __restrict__ vals,      // pad value = 0
           const double* __restrict__ x,
           double* __restrict__ y,
           double* __restrict__ partials,
@@ -199,7 +203,7 @@ k_spmv_sell(long nslices, long nrows, long rowbase,
     for (long s = wslice; s < nslices; s += nw) {
         const long base = sellptr[s];
         const long len = (sellptr[s + 1] - base) >> 6;  // entries per row
-        const double* __restrict__ v = vals + base + lane;
+        const ValT* __restrict__ v = vals + base + lane;
         const ColT* __restrict__ c = cols + base + lane;
         double sum = 0.0;
         long j = 0;
@@ -207,7 +211,7 @@ k_spmv_sell(long nslices, long nrows, long rowbase,
             double a[UNROLL], xx[UNROLL];
             #pragma unroll
             for (int u = 0; u < UNROLL; ++u) {
-                a[u] = NT ? ld_nt(v + (j + u) * WAVE) : v[(j + u) * WAVE];
+                a[u] = (double)(NT ? ld_nt(v + (j + u) * WAVE) : v[(j + u) * WAVE]);
                 const ColT ci = NT ? ld_nt(c + (j + u) * WAVE) : c[(j + u) * WAVE];
                 xx[u] = x[ci];
             }
@@ -215,7 +219,7 @@ k_spmv_sell(long nslices, long nrows, long rowbase,
             for (int u = 0; u < UNROLL; ++u) sum += a[u] * xx[u];
         }
         for (; j < len; ++j) {
-            const double a = NT ? ld_nt(v + j * WAVE) : v[j * WAVE];
+            const double a = (double)(NT ? ld_nt(v + j * WAVE) : v[j * WAVE]);
             const ColT ci = NT ? ld_nt(c + j * WAVE) : c[j * WAVE];
             sum += a * x[ci];
         }
@@ -248,6 +252,9 @@ k_spmv_sell(long nslices, long nrows, long rowbase,
 //     bptr[s]*dof^2 + j*dof^2*64 + bval_off(k, lane)
 //   with bval_off = (k/2)*128 + lane*2 + (k&1) for paired k, and the odd
 //   tail element (k = dof^2-1 when dof^2 is odd) at (dof^2-1)*64 + lane.
+//   fp32-stored values (ValT = float) keep exactly this element order: a
+//   lane's pair is then one 8 B load and a dof-3 block 40 B instead of 76.
+//   Values widen to fp64 on load (exact); all arithmetic stays fp64.
 __device__ __forceinline__ long stencil_col_node(
     int xi, int yi, int zi, int dx, int dy, int dz, int gx, int gy, int gz,
     const long* __restrict__ pb);  // defined with the stencil generators below
@@ -259,12 +266,12 @@ __device__ __forceinline__ long bval_off(int k, int lane) {
                       : (long)EVEN * WAVE + lane;
 }
 
-template <int DOF, bool FUSE_DOT>
+template <int DOF, bool FUSE_DOT, typename ValT = double>
 __global__ void __launch_bounds__(BLOCK)
 k_spmv_bsell(long nslices, long nnodes,
              const long* __restrict__ bptr,
              const int* __restrict__ bcol,
-             const double* __restrict__ bvals,
+             const ValT* __restrict__ bvals,
              const double* __restrict__ x,
              double* __restrict__ y,
              double* __restrict__ partials) {
@@ -276,7 +283,7 @@ k_spmv_bsell(long nslices, long nnodes,
         const long b0 = bptr[s];
         const long blen = (bptr[s + 1] - b0) >> 6;  // blocks per node
         const int* __restrict__ c = bcol + b0 + lane;
-        const double* __restrict__ v = bvals + b0 * (DOF * DOF);
+        const ValT* __restrict__ v = bvals + b0 * (DOF * DOF);
         double acc[DOF];
         #pragma unroll
         for (int r = 0; r < DOF; ++r) acc[r] = 0.0;
@@ -285,10 +292,10 @@ k_spmv_bsell(long nslices, long nnodes,
             double xv[DOF];
             #pragma unroll
             for (int cc = 0; cc < DOF; ++cc) xv[cc] = x[(long)cb * DOF + cc];
-            const double* __restrict__ vj = v + j * (DOF * DOF) * WAVE;
+            const ValT* __restrict__ vj = v + j * (DOF * DOF) * WAVE;
             #pragma unroll
             for (int k = 0; k < DOF * DOF; ++k) {
-                const double a = ld_nt(vj + bval_off<DOF * DOF>(k, lane));
+                const double a = (double)ld_nt(vj + bval_off<DOF * DOF>(k, lane));
                 acc[k / DOF] += a * xv[k % DOF];
             }
         }
@@ -911,12 +918,34 @@ k_stencil_fill(long nrows_nodes, long row0_node, int gx, int gy, int gz,
 void spmv_bsell(long nslices, long nnodes, int dof, uintptr_t bptr,
                 uintptr_t bcol, uintptr_t bvals, uintptr_t x, uintptr_t y,
                 uintptr_t partials, uintptr_t scal, int dotslot,
-                bool dot_accum, uintptr_t stream) {
+                bool dot_accum, bool val32, uintptr_t stream) {
     if (nnodes == 0) return;
     long blocks = (nslices * WAVE + BLOCK - 1) / BLOCK;
     if (blocks > MAXG) blocks = MAXG;
     const bool fuse = partials != 0 && dotslot >= 0;
     dim3 g((unsigned)blocks), b(BLOCK);
+    if (val32) {
+        // fp32-stored values, same pair-major element order
+        #define LBS32(D, FD) \
+            hipLaunchKernelGGL((k_spmv_bsell<D, FD, float>), g, b, 0, (hipStream_t)stream, \
+                nslices, nnodes, (const long*)bptr, (const int*)bcol, \
+                (const float*)bvals, (const double*)x, (double*)y, (double*)partials)
+        switch (dof) {
+            case 2: if (fuse) { LBS32(2, true); } else { LBS32(2, false); } break;
+            case 3: if (fuse) { LBS32(3, true); } else { LBS32(3, false); } break;
+            case 4: if (fuse) { LBS32(4, true); } else { LBS32(4, false); } break;
+            default: throw std::runtime_error("spmv_bsell: dof must be 2/3/4");
+        }
+        #undef LBS32
+        check_hip("spmv_bsell_f32");
+        if (fuse) {
+            hipLaunchKernelGGL(k_reduce_partials, dim3(1), dim3(BLOCK), 0,
+                               (hipStream_t)stream, (const double*)partials,
+                               (int)blocks, (double*)scal, dotslot, dot_accum ? 1 : 0);
+            check_hip("spmv_bsell_reduce");
+        }
+        return;
+    }
     #define LBS(D, FD) \
         hipLaunchKernelGGL((k_spmv_bsell<D, FD>), g, b, 0, (hipStream_t)stream, \
             nslices, nnodes, (const long*)bptr, (const int*)bcol, \
@@ -1781,12 +1810,38 @@ void spmv_sell(long nslices, long nrows, long rowbase, uintptr_t sellptr,
                uintptr_t cols, int col64, uintptr_t vals, uintptr_t x,
                uintptr_t y, bool accum, uintptr_t partials, uintptr_t scal,
                int dotslot, bool dot_accum, int variant, uintptr_t perm,
-               uintptr_t stream) {
+               bool val32, uintptr_t stream) {
     if (nrows == 0) return;
     long blocks = (nslices * WAVE + BLOCK - 1) / BLOCK;
     if (blocks > MAXG) blocks = MAXG;
     const bool fuse = partials != 0 && dotslot >= 0;
     dim3 g((unsigned)blocks), b(BLOCK);
+    if (val32) {
+        // fp32-stored values: only the default flavour (NT, no SWZ,
+        // unroll 8), plain or sigma-perm, is instantiated
+        if ((variant & (SELL_NT | SELL_SWZ | SELL_U8)) != (SELL_NT | SELL_U8))
+            throw std::invalid_argument(
+                "spmv_sell: fp32 values support only variant NT|U8");
+        #define LAUNCH_SELL32(CT, AC, FD, PM) \
+            hipLaunchKernelGGL((k_spmv_sell<CT, AC, FD, true, false, 8, PM, float>), \
+                g, b, 0, S(stream), nslices, nrows, rowbase, \
+                (const long*)sellptr, (const CT*)cols, (const float*)vals, \
+                (const double*)x, (double*)y, (double*)partials, (const int*)perm)
+        #define DISP32_PM(CT, AC, FD) \
+            if (perm != 0) { LAUNCH_SELL32(CT, AC, FD, true); } \
+            else { LAUNCH_SELL32(CT, AC, FD, false); }
+        #define DISP32(CT) \
+            if (accum) { if (fuse) { DISP32_PM(CT, true, true) } else { DISP32_PM(CT, true, false) } } \
+            else       { if (fuse) { DISP32_PM(CT, false, true) } else { DISP32_PM(CT, false, false) } }
+        if (col64) { DISP32(long) } else { DISP32(int) }
+        #undef DISP32
+        #undef DISP32_PM
+        #undef LAUNCH_SELL32
+        check_hip("spmv_sell_f32");
+        if (fuse)
+            reduce_partials(partials, (int)blocks, scal, dotslot, dot_accum, stream);
+        return;
+    }
     if (perm != 0) {
         // sigma-sorted SELL (irregular rows): fixed NT, no swizzle;
         // UNROLL honours the U8 variant bit (deeper unroll = more

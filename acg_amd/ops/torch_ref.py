@@ -18,6 +18,16 @@ S_NSLOTS = 8
 # half-size of the two-phase reduction scratch (shared with kernels.hip);
 # only sell_pipe/pipelined_finalize stage partial sums in this module
 MAXG = 16384
+# storage types of the SELL / BSELL operator values (same as gpu_ops):
+# fp32 values are upcast (exact) and then take the fp64 arithmetic below
+OPERATOR_VALUE_DTYPES = (torch.float64, torch.float32)
+
+
+def _vals64(vals, what: str):
+    if vals.dtype not in OPERATOR_VALUE_DTYPES:
+        raise TypeError(f"{what}: operator values must be float64 or "
+                        f"float32, got {vals.dtype}")
+    return vals.to(torch.float64)
 
 
 def alloc_scalars(device="cpu") -> torch.Tensor:
@@ -299,6 +309,7 @@ def spmv_sell(sellptr, cols, vals, nrows, x, y, *, rowbase: int = 0,
               variant=None, perm=None) -> None:
     """``variant`` only selects a kernel flavour on the GPU (same result);
     ``perm`` maps SELL row -> matrix row (sentinel nrows on pad lanes)."""
+    vals = _vals64(vals, "spmv_sell")
     nslices = sellptr.numel() - 1
     assert (nrows + C - 1) // C == nslices, \
         f"SELL structure was built with a different chunk size than C={C}"
@@ -358,6 +369,7 @@ def _bsell_contrib(bptr, bcol, bvals, nnodes: int, dof: int, xg, C: int = 64):
 def spmv_bsell(bptr, bcol, bvals, nnodes: int, dof: int, x, y, *,
                partials=None, scal=None, dotslot: int = -1,
                dot_accum: bool = True) -> None:
+    bvals = _vals64(bvals, "spmv_bsell")
     if bptr.numel() - 1 <= 0:
         return
     n = nnodes * dof

@@ -7,6 +7,7 @@ iterations, b/r0/r 2-norms, per-op seconds/flops/bytes, halo traffic.
 
 from __future__ import annotations
 
+import math
 from dataclasses import dataclass, field
 
 
@@ -44,6 +45,7 @@ class SolveResult:
     halo_bytes_sent: int = 0
     halo_msgs_sent: int = 0
     nranks: int = 1
+    nouter: int = 0  # mixed-precision refinement sweeps (0 = not refined)
 
     @property
     def iters_per_s(self) -> float:
@@ -65,6 +67,9 @@ class SolveResult:
             f"solve time: {self.tsolve:.6f} s"
             f" ({self.iters_per_s:.2f} it/s, {self.gflops:.1f} Gflop/s)",
         ]
+        if self.nouter:
+            lines.insert(3, f"outer refinement sweeps: {self.nouter} "
+                            f"({self.niterations} inner iterations)")
         if self.halo_bytes_sent:
             per_it = self.halo_bytes_sent / max(self.niterations, 1)
             lines.append(
@@ -76,6 +81,47 @@ class SolveResult:
                     f"  {name}: {op.seconds:.4f} s / {op.count} calls"
                     f" ({op.gbytes_rate:.1f} GB/s, {op.gflops_rate:.1f} Gflop/s)")
         return "\n".join(lines)
+
+
+def refine(res: SolveResult, tol: float, maxits: int, inner_rtol: float,
+           max_outer: int, residual_norm, inner_solve) -> int:
+    """Outer loop of mixed-precision iterative refinement, shared by the
+    CPU and GPU solvers so both take the same decisions.
+
+    ``residual_norm()`` returns the all-reduced true ``||b - A x||`` of the
+    current x with the fp64 operator; ``inner_solve(target, budget)`` solves
+    ``A_lo d = r`` from d = 0 to the absolute residual ``target`` in at most
+    ``budget`` iterations, applies ``x += d`` and returns the iterations it
+    used.  Every decision uses all-reduced scalars only, so all ranks take
+    the same branch.  Fills niterations / nouter / r0nrm2 / rnrm2 /
+    converged of ``res`` and returns the number of residual evaluations.
+
+    The sweep target ``max(inner_rtol*||r||, 0.5*tol)`` keeps the last sweep
+    from over-solving; a residual that does not halve between sweeps means
+    the low-precision operator is too far from A (kappa * 2^-24 not small)
+    and the loop stops unconverged instead of spinning."""
+    nrm = residual_norm()
+    nres = 1
+    res.r0nrm2 = nrm
+    prev = None
+    while True:
+        if not math.isfinite(nrm):
+            raise FloatingPointError(f"refinement diverged: ||r||={nrm}")
+        if nrm <= tol:
+            res.converged = True
+            break
+        if res.nouter >= max_outer or res.niterations >= maxits:
+            break
+        if prev is not None and nrm > 0.5 * prev:
+            break  # stagnated
+        target = max(inner_rtol * nrm, 0.5 * tol)
+        res.niterations += inner_solve(target, maxits - res.niterations)
+        res.nouter += 1
+        prev = nrm
+        nrm = residual_norm()
+        nres += 1
+    res.rnrm2 = nrm
+    return nres
 
 
 def cg_flops_per_iter(nnz_full: int, n: int) -> float:

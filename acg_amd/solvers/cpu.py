@@ -23,7 +23,7 @@ import torch
 from ..dist.halo import HaloExchange
 from ..ops import torch_ref as ops
 from ..part.subdomain import LocalSystem
-from .base import SolveResult, cg_flops_per_iter
+from .base import SolveResult, cg_flops_per_iter, refine
 
 
 class CGSolverCPU:
@@ -43,6 +43,7 @@ class CGSolverCPU:
         self.halo = HaloExchange(L.halo, L.nowned, self.device, comm)
         self.n = L.nowned
         self.nlocal = L.nowned + L.nghost
+        self._A_vals32 = None  # fp32 copy of the matA values (solve_mixed)
 
     # -- helpers ----------------------------------------------------------
 
@@ -55,10 +56,18 @@ class CGSolverCPU:
         v = torch.dot(a[: self.n], b[: self.n]).reshape(1)
         return float(self._allreduce(v)[0])
 
-    def _spmv(self, xfull: torch.Tensor, y: torch.Tensor) -> None:
-        """y = A_local x (halo exchange + split matA/matO SpMV)."""
+    def _spmv(self, xfull: torch.Tensor, y: torch.Tensor,
+              lowprec: bool = False) -> None:
+        """y = A_local x (halo exchange + split matA/matO SpMV).
+        ``lowprec``: matA values rounded to fp32 storage (widened back
+        exactly, fp64 arithmetic); matO stays fp64 as on the GPU."""
         self.halo.exchange(xfull)
-        ops.spmv(self.A_rowptr, self.A_colidx, self.A_vals, xfull, y)
+        avals = self.A_vals
+        if lowprec:
+            if self._A_vals32 is None:
+                self._A_vals32 = self.A_vals.to(torch.float32)
+            avals = self._A_vals32.to(torch.float64)
+        ops.spmv(self.A_rowptr, self.A_colidx, avals, xfull, y)
         ops.spmv(self.O_rowptr, self.O_colidx, self.O_vals, xfull, y,
                  rowbase=self.local.ninterior, accum=True)
 
@@ -71,6 +80,12 @@ class CGSolverCPU:
     def solve(self, b: torch.Tensor, x: torch.Tensor, maxits: int = 100,
               res_atol: float = 0.0, res_rtol: float = 1e-9,
               diff_atol: float = 0.0, diff_rtol: float = 0.0) -> SolveResult:
+        return self._solve_classic(b, x, maxits, res_atol, res_rtol,
+                                   diff_atol, diff_rtol, lowprec=False)
+
+    def _solve_classic(self, b, x, maxits, res_atol, res_rtol,
+                       diff_atol=0.0, diff_rtol=0.0, *,
+                       lowprec: bool) -> SolveResult:
         res = SolveResult(solver="cg-cpu", maxits=maxits, res_atol=res_atol,
                           res_rtol=res_rtol,
                           nranks=self.comm.size if self.comm else 1)
@@ -82,7 +97,7 @@ class CGSolverCPU:
         t = self._vec()
         p = self._vec(nghost=True)
         # r0 = b - A x0
-        self._spmv(x, t)
+        self._spmv(x, t, lowprec)
         r[:] = b[:n] - t
         p[:n] = r
         rr = self._dot(r, r)
@@ -95,7 +110,7 @@ class CGSolverCPU:
             res.tsolve = time.perf_counter() - t0
             return res
         for k in range(maxits):
-            self._spmv(p, t)
+            self._spmv(p, t, lowprec)
             pt = self._dot(p, t)
             alpha = rr / pt if pt != 0.0 else 0.0  # 0/0 at underflow: freeze
             r -= alpha * t
@@ -120,6 +135,55 @@ class CGSolverCPU:
         res.tsolve = time.perf_counter() - t0
         nnz_full = self.local.nnzA + self.local.nnzO
         res.nflops = res.niterations * cg_flops_per_iter(nnz_full, n)
+        res.halo_bytes_sent = self.halo.bytes_sent
+        res.halo_msgs_sent = self.halo.nmsgs_sent
+        return res
+
+    # -- mixed precision: fp32-stored operator + fp64 refinement (beyond
+    # reference; the oracle of CGSolverHIP.solve_mixed) -------------------
+
+    def solve_mixed(self, b: torch.Tensor, x: torch.Tensor, maxits: int = 100,
+                    res_atol: float = 0.0, res_rtol: float = 1e-9,
+                    inner_rtol: float = 1e-6,
+                    max_outer: int = 20) -> SolveResult:
+        """CG on the fp32-rounded matA values wrapped in fp64 iterative
+        refinement (see base.refine): r = b - A x with the fp64 operator,
+        classic CG on ``A_lo d = r`` from d = 0 down to
+        ``max(inner_rtol*||r||, 0.5*tol)``, x += d; at most ``max_outer``
+        sweeps and ``maxits`` inner iterations in total.  ``niterations``
+        counts inner iterations, ``nouter`` sweeps, ``rnrm2`` is the true
+        fp64 residual norm of the returned x."""
+        res = SolveResult(solver="cg-cpu-mixed", maxits=maxits,
+                          res_atol=res_atol, res_rtol=res_rtol,
+                          nranks=self.comm.size if self.comm else 1)
+        n = self.n
+        t0 = time.perf_counter()
+        res.bnrm2 = math.sqrt(self._dot(b, b))
+        tol = max(res_atol, res_rtol * res.bnrm2)
+        r = self._vec()
+        t = self._vec()
+        d = self._vec(nghost=True)
+
+        def residual_norm() -> float:
+            self._spmv(x, t)
+            torch.sub(b[:n], t, out=r)
+            return math.sqrt(self._dot(r, r))
+
+        def inner_solve(target: float, budget: int) -> int:
+            d.zero_()
+            inner = self._solve_classic(r, d, budget, target, 0.0,
+                                        lowprec=True)
+            x[:n] += d[:n]
+            return inner.niterations
+
+        nres = refine(res, tol, maxits, inner_rtol, max_outer,
+                      residual_norm, inner_solve)
+        res.tsolve = time.perf_counter() - t0
+        nnz_full = self.local.nnzA + self.local.nnzO
+        # every sweep adds the fp64 residual SpMV and the inner solve's
+        # initial SpMV; one more residual closes the loop
+        res.nflops = (res.niterations * cg_flops_per_iter(nnz_full, n)
+                      + (nres + res.nouter) * (2.0 * nnz_full + 3.0 * n))
         res.halo_bytes_sent = self.halo.bytes_sent
         res.halo_msgs_sent = self.halo.nmsgs_sent
         return res

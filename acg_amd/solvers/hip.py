@@ -33,7 +33,7 @@ import torch
 from ..dist.halo import HaloExchange
 from ..ops import gpu_ops as ops
 from ..part.subdomain import LocalSystem
-from .base import SolveResult, cg_flops_per_iter
+from .base import SolveResult, cg_flops_per_iter, refine
 
 
 class CGSolverHIP:
@@ -136,6 +136,7 @@ class CGSolverHIP:
         self._ws: dict = {}
         self._graphs: dict = {}
         self._nstag = 0
+        self._vals32 = None  # fp32 matA values, built by _lowprec_values
 
     def _pick_format(self, L, up, use_sell: bool, force: str | None) -> None:
         """Choose the matA operator format (reference analog: the choice
@@ -270,11 +271,46 @@ class CGSolverHIP:
         if self.comm is not None and self.comm.size > 1:
             self.comm.allreduce_(self.scal[slot:slot + count])
 
+    def _format_name(self) -> str:
+        if self.matfree is not None:
+            return "matrix-free"
+        if hasattr(self.local, "A_sell"):
+            return "device-generated"
+        if self.bsell is not None:
+            return "bsell"
+        if self.sell is not None:
+            return "sigma" if self.sell_perm is not None else "sell"
+        if self.hybrid is not None:
+            return "hybrid" if self.hybrid["sellptr"] is not None else "binned"
+        return "csr"
+
+    def _lowprec_values(self) -> torch.Tensor:
+        """fp32 copy of the matA values of the chosen format (plain SELL,
+        sigma-SELL or BSELL), built on first use.  Same element order, so
+        the cast is the whole pack step.  The fp64 values are KEPT --
+        refinement needs the exact residual -- so a solver that uses the
+        fp32 operator holds 1.5x the value memory.  matO stays fp64."""
+        if self._vals32 is None and self.n == 0:  # rank without rows
+            self._vals32 = torch.empty(0, dtype=torch.float32,
+                                       device=self.device)
+        if self._vals32 is None:
+            fmt = self._format_name()
+            if fmt not in ("sell", "sigma", "bsell"):
+                raise ValueError(
+                    f"the fp32-stored operator needs the SELL, sigma-SELL or "
+                    f"BSELL format; this system uses {fmt}")
+            src = self.bsell[2] if self.bsell is not None else self.sell[2]
+            self._vals32 = src.to(torch.float32)
+        return self._vals32
+
     def _spmv_overlapped(self, xfull: torch.Tensor, y: torch.Tensor,
-                         fuse_dotslot: int = -1):
+                         fuse_dotslot: int = -1, lowprec: bool = False):
         """halo(x) on comm stream overlapped with SpMV(matA); SpMV(matO)
-        after the ghost tail arrives.  Mirrors reference cghip.c:887-931."""
+        after the ghost tail arrives.  Mirrors reference cghip.c:887-931.
+        ``lowprec`` selects the fp32-stored matA values (see
+        _lowprec_values); the default is the fp64 operator."""
         L = self.local
+        vals32 = self._lowprec_values() if lowprec else None
         have_halo = self.comm is not None and self.comm.size > 1
         cur = torch.cuda.current_stream(self.device)
         halo_span = None
@@ -296,10 +332,14 @@ class CGSolverHIP:
                                  mato=False, dot_accum=False, **fuse)
             elif self.bsell is not None:
                 bptr, bcol, bvals, dof = self.bsell
-                ops.spmv_bsell(bptr, bcol, bvals, self.n // dof, dof,
+                ops.spmv_bsell(bptr, bcol,
+                               bvals if vals32 is None else vals32,
+                               self.n // dof, dof,
                                xfull, y, dot_accum=False, **fuse)
             elif self.sell is not None:
                 sellptr, scols, svals = self.sell
+                if vals32 is not None:
+                    svals = vals32
                 ops.spmv_sell(sellptr, scols, svals, self.n, xfull, y,
                               accum=False, perm=self.sell_perm,
                               dot_accum=False, **fuse)
@@ -392,6 +432,19 @@ class CGSolverHIP:
         tolerances, cghip.c:427); engaging it switches to a blocking
         per-iteration host test (no lag pipeline, no graph replay).
         """
+        return self._solve_classic(b, x, maxits, res_atol, res_rtol,
+                                   use_graph, fold_daypx, diff_atol,
+                                   diff_rtol, lowprec=False)
+
+    def _solve_classic(self, b, x, maxits, res_atol, res_rtol,
+                       use_graph=None, fold_daypx=None, diff_atol=0.0,
+                       diff_rtol=0.0, *, lowprec: bool) -> SolveResult:
+        """The classic iteration behind :meth:`solve`.  ``lowprec`` runs
+        every SpMV on the fp32-stored matA values (the inner solver of
+        :meth:`solve_mixed`); captured graphs are keyed per value set, so
+        a graph recorded with one operator is never replayed for the
+        other."""
+        gkey = "classic:f32" if lowprec else "classic"
         res = SolveResult(solver="cg-hip", maxits=maxits, res_atol=res_atol,
                           res_rtol=res_rtol,
                           nranks=self.comm.size if self.comm else 1)
@@ -408,7 +461,7 @@ class CGSolverHIP:
         S.dot(b, b, self.partials, scal, S.S_BNRM2, n=n)
         self._allreduce_slot(S.S_BNRM2)
         # r0 = b - A x0;  p = r0
-        self._spmv_overlapped(xi, t)
+        self._spmv_overlapped(xi, t, lowprec=lowprec)
         torch.sub(b[:n], t, out=r)
         p[:n] = r
         S.dot(r, r, self.partials, scal, S.S_RR, n=n)
@@ -445,9 +498,9 @@ class CGSolverHIP:
         if use_graph is None:
             use_graph = not serial  # measured policy (see docstring)
         graph_ok = use_graph and serial and not self.prof.enabled and not fold
-        graph = self._graphs.get("classic") if graph_ok else None
+        graph = self._graphs.get(gkey) if graph_ok else None
         # multi-GPU: capture the whole distributed iteration (see docstring)
-        dist_key = "classic:dist"
+        dist_key = gkey + ":dist"
         dist_failed_key = "classic:capture_failed"
         dist_graph_ok = (use_graph and not serial and not self.prof.enabled
                          and not fold
@@ -479,7 +532,7 @@ class CGSolverHIP:
                 return
             # halo+split SpMV with the (p,t) reduction fused into both
             # passes (matA overwrites the slot, matO accumulates)
-            self._spmv_overlapped(p, t, fuse_dotslot=S.S_PT)
+            self._spmv_overlapped(p, t, fuse_dotslot=S.S_PT, lowprec=lowprec)
             with self.prof.span("allreduce"):
                 self._allreduce_slot(S.S_PT)
             # fused r/x update (alpha = rr/pt on device) + combined
@@ -522,7 +575,7 @@ class CGSolverHIP:
                     graph = torch.cuda.CUDAGraph()
                     with torch.cuda.graph(graph):
                         body()
-                    self._graphs["classic"] = graph
+                    self._graphs[gkey] = graph
                 elif dist_graph_ok and k == 2 and dgraph is None:
                     # RCCL channels are warm after 2 eager iterations;
                     # capture records without executing (rank-local)
@@ -615,6 +668,77 @@ class CGSolverHIP:
             annotate_op_stats(res, self.local, self.prof.collect(),
                               idx_bytes_per_nnz=idxb)
             self.prof.reset()
+        return res
+
+    # -- mixed precision: fp32-stored operator + fp64 refinement (beyond
+    # reference; opt-in, no auto-selection) -------------------------------
+
+    def solve_mixed(self, b: torch.Tensor, x: torch.Tensor, maxits: int = 100,
+                    res_atol: float = 0.0, res_rtol: float = 1e-9,
+                    inner_rtol: float = 1e-6,
+                    max_outer: int = 20) -> SolveResult:
+        """Classic CG on the fp32-STORED matA values wrapped in fp64
+        iterative refinement (oracle: CGSolverCPU.solve_mixed; loop:
+        base.refine).  The SpMV is at the HBM roofline and the values are
+        its largest stream: fp32 storage cuts a dof-3 BSELL block from 76
+        to 40 B and a SELL entry from 12 to 8 B, while every vector, product
+        and sum stays fp64.  Each sweep computes r = b - A x with the fp64
+        operator, solves ``A_lo d = r`` from d = 0 with the classic
+        iteration to ``max(inner_rtol*||r||, 0.5*tol)`` and adds d to x.
+
+        Needs the plain SELL, sigma-SELL or BSELL format (ValueError names
+        any other) and keeps BOTH value sets: 1.5x the value memory.
+        ``niterations`` counts inner iterations (at most ``maxits`` in
+        total), ``nouter`` the sweeps; ``rnrm2`` is the TRUE fp64 residual
+        norm of the returned x.  ``fold_daypx`` and the diff tolerances are
+        not offered here.
+
+        ``inner_rtol`` default 1e-6 is MEASURED (profiles/mixed_precision.md,
+        scaled Queen-shaped system: -15% / -19% time-to-solution at rtol
+        1e-9 / 1e-12 against 1e-4's -10% / -13%): a sweep costs 3-4
+        iteration equivalents, so few deep sweeps beat many shallow ones."""
+        self._lowprec_values()  # unsupported format: fail before any work
+        res = SolveResult(solver="cg-hip-mixed", maxits=maxits,
+                          res_atol=res_atol, res_rtol=res_rtol,
+                          nranks=self.comm.size if self.comm else 1)
+        n = self.n
+        S = ops
+        scal = self.scal
+        ws = self._workspace("mixed", [("ro", False), ("to", False),
+                                       ("d", True)])
+        ro, to, d = ws["ro"], ws["to"], ws["d"]
+        torch.cuda.synchronize(self.device)
+        t0 = time.perf_counter()
+        S.dot(b, b, self.partials, scal, S.S_BNRM2, n=n)
+        self._allreduce_slot(S.S_BNRM2)
+        res.bnrm2 = math.sqrt(max(self._host_scalar(S.S_BNRM2), 0.0))
+        tol = max(res_atol, res_rtol * res.bnrm2)
+
+        def residual_norm() -> float:
+            self._spmv_overlapped(x, to)
+            torch.sub(b[:n], to, out=ro)
+            S.dot(ro, ro, self.partials, scal, S.S_RR, n=n)
+            self._allreduce_slot(S.S_RR)
+            return math.sqrt(max(self._host_scalar(S.S_RR), 0.0))
+
+        def inner_solve(target: float, budget: int) -> int:
+            d.zero_()
+            inner = self._solve_classic(ro, d, budget, target, 0.0,
+                                        lowprec=True)
+            x[:n] += d[:n]
+            return inner.niterations
+
+        nres = refine(res, tol, maxits, inner_rtol, max_outer,
+                      residual_norm, inner_solve)
+        torch.cuda.synchronize(self.device)
+        res.tsolve = time.perf_counter() - t0
+        nnz_full = self.local.nnzA + self.local.nnzO
+        # every sweep adds the fp64 residual SpMV and the inner solve's
+        # initial SpMV; one more residual closes the loop
+        res.nflops = (res.niterations * cg_flops_per_iter(nnz_full, n)
+                      + (nres + res.nouter) * (2.0 * nnz_full + 3.0 * n))
+        res.halo_bytes_sent = self.halo.bytes_sent
+        res.halo_msgs_sent = self.halo.nmsgs_sent
         return res
 
     # -- monolithic device-side CG ---------------------------------------

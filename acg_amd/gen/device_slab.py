@@ -78,19 +78,22 @@ def preflight_slab(gx: int, gy: int, gz: int, spec: dict, rank: int,
     return est
 
 
-def device_stencil_slab(gx: int, gy: int, gz: int, spec: dict,
-                        rank: int, nranks: int, device,
-                        operator: bool = True) -> DeviceSlabSystem:
-    """``operator=False`` skips assembling the SELL/BSELL arrays (row
-    lengths are still counted for nnz stats): matrix-free solves (dof=1)
-    need no memory-resident operator at all, freeing the ~12 B/nnz for
-    larger grids per GPU."""
-    from ..ops import gpu_ops
+def stencil_slab_tables(gx: int, gy: int, gz: int, spec: dict,
+                        rank: int, nranks: int) -> dict:
+    """Host-side tables of rank ``rank``'s z-slab: plane ordering, counts,
+    stencil offsets and blocks.  Needs no GPU and no compiled extension;
+    :func:`device_stencil_slab` uploads them, CPU tests build the
+    matrix-free ``mf`` dict from them (:func:`mf_tables_from`).
 
-    K = gpu_ops.K
-    device = torch.device(device)
+    pb: plane z (+1 shift) -> local node base, -1 if absent (int64[gz+2]);
+    zs_own: local owned plane -> z (int32); offs: (dx, dy, dz, w) per
+    offset, flattened; blocks: M then D, dof*dof each; w7: the per-axis
+    weights (-x, +x, -y, +y, -z, +z) of a 7-point stencil, else None."""
     dof = spec["dof"]
     M, D = _blocks(spec)
+    maxreach = max((abs(int(o[2])) for o in spec["offsets"]), default=0)
+    if maxreach > 1:
+        raise ValueError("slab generator supports |dz| <= 1 stencils")
     z0, z1 = _slab_bounds(gz, rank, nranks)
     nz_own = z1 - z0
     if nz_own <= 0:
@@ -103,28 +106,81 @@ def device_stencil_slab(gx: int, gy: int, gz: int, spec: dict,
     ghost_planes = ([z0 - 1] if has_lo else []) + ([z1] if has_hi else [])
     plane_seq = interior_planes + border_planes + ghost_planes
 
-    nown_nodes = nz_own * plane_nodes
-    ninterior_nodes = len(interior_planes) * plane_nodes
-    nborder_nodes = len(border_planes) * plane_nodes
-    nghost_nodes = len(ghost_planes) * plane_nodes
-    nowned = nown_nodes * dof
-    nghost = nghost_nodes * dof
-    assert (nowned + nghost) * 1 < 2**31, "device generator needs int32 local cols"
-
-    # plane tables
     pb = torch.full((gz + 2,), -1, dtype=torch.int64)
     for k, z in enumerate(plane_seq):
         pb[z + 1] = k * plane_nodes
     zs_own = torch.tensor([z for z in interior_planes + border_planes],
                           dtype=torch.int32)
-    pb = pb.to(device)
-    zs_own = zs_own.to(device)
     offs_np = np.asarray([[dx, dy, dz, w] for (dx, dy, dz, w) in spec["offsets"]],
                          dtype=np.float64)
-    offs = torch.from_numpy(offs_np).reshape(-1).to(device)
     ksten = len(spec["offsets"])
-    blocks = torch.from_numpy(
-        np.concatenate([M.reshape(-1), D.reshape(-1)])).to(device)
+    # 7-pt fast path: the z-column-walk kernels need the per-axis weights
+    # and the slab bounds (w_old is then read exactly once, with the
+    # z +- 1 neighbours carried in registers).
+    w7 = None
+    if ksten == 6:
+        wmap = {(int(dx), int(dy), int(dz)): float(w)
+                for (dx, dy, dz, w) in spec["offsets"]}
+        keys = [(-1, 0, 0), (1, 0, 0), (0, -1, 0),
+                (0, 1, 0), (0, 0, -1), (0, 0, 1)]
+        if set(wmap) == set(keys):
+            w7 = tuple(wmap[k] for k in keys)
+    return dict(
+        dof=dof, gx=gx, gy=gy, gz=gz, z0=z0, z1=z1, plane_nodes=plane_nodes,
+        has_lo=has_lo, has_hi=has_hi, plane_seq=plane_seq,
+        nown_nodes=nz_own * plane_nodes,
+        ninterior_nodes=len(interior_planes) * plane_nodes,
+        nborder_nodes=len(border_planes) * plane_nodes,
+        nghost_nodes=len(ghost_planes) * plane_nodes,
+        pb=pb, zs_own=zs_own, offs=torch.from_numpy(offs_np).reshape(-1),
+        ksten=ksten, w7=w7, diag=float(D[0, 0]),
+        blocks=torch.from_numpy(np.concatenate([M.reshape(-1), D.reshape(-1)])))
+
+
+def mf_tables_from(tab: dict, zs_own, pb, offs):
+    """Matrix-free operator tables (dof=1 constant-coefficient stencils):
+    everything k_stencil_spmv / k_stencil_pipe need to apply the operator
+    without any assembled matrix (ops.gpu_ops.stencil_spmv); ``zs_own``,
+    ``pb``, ``offs`` are the tables of ``tab`` on the device that applies
+    the operator.  None for block operators."""
+    if tab["dof"] != 1:
+        return None
+    return dict(zs=zs_own, pb=pb, offs=offs, ksten=tab["ksten"],
+                diag=tab["diag"], gx=tab["gx"], gy=tab["gy"], gz=tab["gz"],
+                nown_nodes=tab["nown_nodes"], z0=tab["z0"], z1=tab["z1"],
+                w7=tab["w7"])
+
+
+def device_stencil_slab(gx: int, gy: int, gz: int, spec: dict,
+                        rank: int, nranks: int, device,
+                        operator: bool = True) -> DeviceSlabSystem:
+    """``operator=False`` skips assembling the SELL/BSELL arrays (row
+    lengths are still counted for nnz stats): matrix-free solves (dof=1)
+    need no memory-resident operator at all, freeing the ~12 B/nnz for
+    larger grids per GPU."""
+    tab = stencil_slab_tables(gx, gy, gz, spec, rank, nranks)
+    from ..ops import gpu_ops
+
+    K = gpu_ops.K
+    device = torch.device(device)
+    dof = tab["dof"]
+    z0, z1 = tab["z0"], tab["z1"]
+    plane_nodes = tab["plane_nodes"]
+    has_lo, has_hi = tab["has_lo"], tab["has_hi"]
+    plane_seq = tab["plane_seq"]
+    nown_nodes = tab["nown_nodes"]
+    ninterior_nodes = tab["ninterior_nodes"]
+    nborder_nodes = tab["nborder_nodes"]
+    nghost_nodes = tab["nghost_nodes"]
+    nowned = nown_nodes * dof
+    nghost = nghost_nodes * dof
+    assert (nowned + nghost) * 1 < 2**31, "device generator needs int32 local cols"
+
+    pb = tab["pb"].to(device)
+    zs_own = tab["zs_own"].to(device)
+    offs = tab["offs"].to(device)
+    ksten = tab["ksten"]
+    blocks = tab["blocks"].to(device)
     stream = torch.cuda.current_stream(device).cuda_stream
 
     def build(filter_ghost: int, nodes: int, row0_node: int):
@@ -162,25 +218,7 @@ def device_stencil_slab(gx: int, gy: int, gz: int, spec: dict,
     A_sellptr, A_cols, A_vals, nnzA = build(0, nown_nodes, 0)
     O_sellptr, O_cols, O_vals, nnzO = build(1, nborder_nodes, ninterior_nodes)
 
-    # matrix-free operator tables (dof=1 constant-coefficient stencils):
-    # everything k_stencil_spmv / k_stencil_pipe need to apply the operator
-    # without any assembled matrix (ops.gpu_ops.stencil_spmv).
-    mf_tables = None
-    if dof == 1:
-        # 7-pt fast path: the z-column-walk kernels need the per-axis
-        # weights and the slab bounds (w_old is then read exactly once,
-        # with the z +- 1 neighbours carried in registers).
-        w7 = None
-        if ksten == 6:
-            wmap = {(int(dx), int(dy), int(dz)): float(w)
-                    for (dx, dy, dz, w) in spec["offsets"]}
-            keys = [(-1, 0, 0), (1, 0, 0), (0, -1, 0),
-                    (0, 1, 0), (0, 0, -1), (0, 0, 1)]
-            if set(wmap) == set(keys):
-                w7 = tuple(wmap[k] for k in keys)
-        mf_tables = dict(zs=zs_own, pb=pb, offs=offs, ksten=ksten,
-                         diag=float(D[0, 0]), gx=gx, gy=gy, gz=gz,
-                         nown_nodes=nown_nodes, z0=z0, z1=z1, w7=w7)
+    mf_tables = mf_tables_from(tab, zs_own, pb, offs)
 
     # Block-SELL for matA when the operator has dense dof x dof blocks:
     # one int32 index per block instead of per entry (4 -> 4/dof^2 B/nnz).

@@ -532,6 +532,89 @@ def sell_pipe(sellptr, cols, vals, nrows_pass: int, rowbase: int,
     return 1
 
 
+def _stencil_contrib(mf, nrows_nodes: int, row0_node: int, x, mato: bool):
+    """Rows row0_node .. row0_node+nrows_nodes of the matrix-free stencil
+    operator applied to the local vector ``x``: the owned couplings and the
+    diagonal (mato=False) or the ghost-plane couplings alone (mato=True).
+    Index arithmetic over the same pb/zs/offs tables the kernels read."""
+    gx, gy, gz = mf["gx"], mf["gy"], mf["gz"]
+    plane_nodes = gx * gy
+    pb, zs = mf["pb"].long(), mf["zs"].long()
+    offs = mf["offs"].view(-1, 4)
+    node = torch.arange(row0_node, row0_node + nrows_nodes, dtype=torch.int64,
+                        device=x.device)
+    rem = node % plane_nodes
+    xi, yi, zi = rem % gx, rem // gx, zs[node // plane_nodes]
+    out = torch.zeros(nrows_nodes, dtype=torch.float64, device=x.device)
+    if not mato:
+        out += mf["diag"] * x[node]
+    for o in range(mf["ksten"]):
+        dx, dy, dz = (int(offs[o, k]) for k in range(3))
+        nx, ny, nz = xi + dx, yi + dy, zi + dz
+        ok = ((nx >= 0) & (nx < gx) & (ny >= 0) & (ny < gy)
+              & (nz >= 0) & (nz < gz))
+        base = pb[nz.clamp(0, gz - 1) + 1]
+        ok &= base >= 0
+        cn = base + nx + gx * ny
+        ok &= (cn >= mf["nown_nodes"]) == mato
+        out[ok] += offs[o, 3] * x[cn[ok]]
+    return out
+
+
+def stencil_spmv(mf, nrows_nodes: int, row0_node: int, x, y, *,
+                 mato: bool = False, partials=None, scal=None,
+                 dotslot: int = -1, dot_accum: bool = True) -> None:
+    """Matrix-free stencil SpMV (matches k_stencil_spmv and, for 7-point
+    stencils, the column walk k_stencil_spmv7): the matA pass stores the
+    owned couplings, the matO pass adds the ghost couplings of its rows."""
+    if nrows_nodes <= 0:
+        return
+    contrib = _stencil_contrib(mf, nrows_nodes, row0_node, x, mato)
+    sl = slice(row0_node, row0_node + nrows_nodes)
+    if mato:
+        y[sl] += contrib
+    else:
+        y[sl] = contrib
+    if scal is not None and dotslot >= 0:
+        d = torch.dot(x[sl], contrib)
+        scal[dotslot] = scal[dotslot] + d if dot_accum else d
+
+
+def stencil_pipe(mf, nrows_nodes: int, row0_node: int, border_base: int,
+                 w_old, qpart, z, t, p, x, r, w_new, scal, first: bool,
+                 partials, partials_off: int, mato: bool) -> int:
+    """One pass of the megafused matrix-free pipelined iteration (matches
+    k_stencil_pipe / k_stencil_pipe7); same qpart / partials protocol as
+    :func:`sell_pipe`, always one block per pass."""
+    if nrows_nodes <= 0:
+        return 0
+    q = _stencil_contrib(mf, nrows_nodes, row0_node, w_old, mato)
+    beta, alpha = _pipelined_coeffs(scal, first)
+    rows = torch.arange(row0_node, row0_node + nrows_nodes, device=w_old.device)
+    if mato:
+        upd = rows
+        qu = q + qpart[upd - border_base]
+    else:
+        defer = rows >= border_base
+        qpart[rows[defer] - border_base] = q[defer]
+        upd = rows[~defer]
+        qu = q[~defer]
+    zi = qu + beta * z[upd]
+    ti = w_old[upd] + beta * t[upd]
+    pi = r[upd] + beta * p[upd]
+    z[upd] = zi
+    t[upd] = ti
+    p[upd] = pi
+    x[upd] += alpha * pi
+    rn = r[upd] - alpha * ti
+    wn = w_old[upd] - alpha * zi
+    r[upd] = rn
+    w_new[upd] = wn
+    partials[partials_off] = torch.dot(rn, rn)
+    partials[MAXG + partials_off] = torch.dot(wn, rn)
+    return 1
+
+
 def pipelined_finalize(partials, nblocks: int, scal, first: bool) -> None:
     """Rotate gamma -> gamma_prev, store alpha -> alpha_prev, publish the
     summed partials as the new gamma/delta (matches k_pipelined_finalize)."""

@@ -6,7 +6,10 @@ Plain helper module (not a conftest).  Three parts:
   the fp64 input vectors in ``np.longdouble`` (when it carries a 64-bit
   significand) or exact ``fractions.Fraction``; each value ``v`` comes with
   a magnitude ``M`` = the same expression with every term replaced by its
-  absolute value;
+  absolute value.  The matrix-free stencil kernels have no CSR: their
+  oracle (:func:`stencil_apply`) applies the stencil from global grid
+  coordinates, and the slab generators are checked entry by entry against
+  :func:`stencil_structure`;
 * acceptance: ``|got_i - v_i| <= (L_i + 48) * 2^-53 * M_i`` element-wise
   (L_i = products summed into element i), propagated bounds for reduced
   scalars, bitwise equality where the result is exactly representable;
@@ -216,6 +219,153 @@ def csr_dense(rowptr, colidx, vals, ncols):
     dense = np.zeros((len(rowptr) - 1, ncols), dtype=np.float64)
     dense[csr_rows(rowptr), np.asarray(colidx, np.int64)] = vals
     return dense
+
+
+def stencil_apply(gx, gy, gz, offsets, diag, xg, part=None):
+    """Constant-coefficient stencil operator from GLOBAL grid coordinates
+    (node id = x + gx*(y + gy*z)): y = diag*x + sum_o w_o * x[shifted by o],
+    out-of-grid neighbours contributing nothing.  Knows nothing of slabs'
+    local numbering, plane tables or any CSR the project builds.
+
+    ``part = (which, z0, z1)`` restricts to the rows of planes [z0, z1) and
+    keeps only the couplings into those planes plus the diagonal
+    (``"owned"``, the matA part) or only the couplings into other planes
+    (``"ghost"``, the matO part).  ``xg`` is an fp64 array of gx*gy*gz
+    values.  Returns flat global (value, magnitude, products per row)."""
+    X = hp(np.asarray(xg, dtype=np.float64)).reshape(gz, gy, gx)
+    aX = habs(X)
+    v = hzeros(gx * gy * gz).reshape(gz, gy, gx)
+    M = hzeros(gx * gy * gz).reshape(gz, gy, gx)
+    L = np.zeros((gz, gy, gx), dtype=np.int64)
+    which, z0, z1 = part if part is not None else (None, 0, gz)
+    if which != "ghost":
+        d = hps(diag)
+        v[z0:z1] += d * X[z0:z1]
+        M[z0:z1] += abs(d) * aX[z0:z1]
+        L[z0:z1] += 1
+    for (dx, dy, dz, w) in offsets:
+        dx, dy, dz = int(dx), int(dy), int(dz)
+        wh = hps(w)
+        ys = slice(max(0, -dy), min(gy, gy - dy))
+        xs = slice(max(0, -dx), min(gx, gx - dx))
+        yt = slice(ys.start + dy, ys.stop + dy)
+        xt = slice(xs.start + dx, xs.stop + dx)
+        if ys.start >= ys.stop or xs.start >= xs.stop:
+            continue
+        for z in range(z0, z1):
+            tz = z + dz
+            if not 0 <= tz < gz:
+                continue
+            if which is not None and (z0 <= tz < z1) != (which == "owned"):
+                continue
+            v[z, ys, xs] += wh * X[tz, yt, xt]
+            M[z, ys, xs] += abs(wh) * aX[tz, yt, xt]
+            L[z, ys, xs] += 1
+    return v.reshape(-1), M.reshape(-1), L.reshape(-1)
+
+
+def stencil_structure(gx, gy, gz, spec, rank, nranks):
+    """Per-row structure oracle for the slab generators: for every owned
+    local row (node, a) the dictionary {local column: value} of its owned
+    couplings (``rowsA``) and, for the border rows, of its ghost couplings
+    (``rowsO``, indexed from the first border row).  Built from global
+    coordinates; value = D[a, b] for the node's own block and w_o * M[a, b]
+    (ONE fp64 product, exactly reproducible) for neighbour o.  Local <->
+    global goes through the host slab's owned_global / ghost_global."""
+    from acg_amd.gen.stencil import stencil_local_slab
+
+    H = stencil_local_slab(gx, gy, gz, spec, rank, nranks)
+    dof = spec["dof"]
+    Mb = np.asarray(spec.get("offblock", np.eye(dof)), dtype=np.float64)
+    Db = np.asarray(spec.get("diagblock", spec.get("diag", 1.0) * np.eye(dof)),
+                    dtype=np.float64)
+    g2l = {int(g): i for i, g in enumerate(
+        np.concatenate([H.owned_global, H.ghost_global]))}
+    assert len(g2l) == H.nowned + H.nghost
+    rowsA, rowsO = [], []
+    for row in range(H.nowned):
+        gnode, a = divmod(int(H.owned_global[row]), dof)
+        x, y, z = gnode % gx, (gnode // gx) % gy, gnode // (gx * gy)
+        dA = {g2l[gnode * dof + b]: float(Db[a, b]) for b in range(dof)}
+        dO = {}
+        for (dx, dy, dz, w) in spec["offsets"]:
+            nx, ny, nz = x + int(dx), y + int(dy), z + int(dz)
+            if not (0 <= nx < gx and 0 <= ny < gy and 0 <= nz < gz):
+                continue
+            nb = nx + gx * (ny + gy * nz)
+            for b in range(dof):
+                col = g2l[nb * dof + b]
+                tgt = dA if col < H.nowned else dO
+                assert col not in tgt
+                tgt[col] = float(w) * float(Mb[a, b])
+        rowsA.append(dA)
+        if row >= H.ninterior:
+            rowsO.append(dO)
+        else:
+            assert not dO, "an interior row couples to a ghost"
+    return SimpleNamespace(dof=dof, rowsA=rowsA, rowsO=rowsO, nowned=H.nowned,
+                           ninterior=H.ninterior, nborder=H.nborder,
+                           nghost=H.nghost, nlocal=H.nowned + H.nghost,
+                           nnzA=sum(map(len, rowsA)), nnzO=sum(map(len, rowsO)))
+
+
+def rows_to_csr(rows):
+    """[{col: value}] -> (rowptr, colidx, vals), columns ascending."""
+    rowptr = np.zeros(len(rows) + 1, dtype=np.int64)
+    np.cumsum([len(d) for d in rows], out=rowptr[1:])
+    cols = np.array([c for d in rows for c in sorted(d)], dtype=np.int64)
+    vals = np.array([d[c] for d in rows for c in sorted(d)], dtype=np.float64)
+    return rowptr, cols, vals
+
+
+def csr_to_rows(rowptr, colidx, vals):
+    out = []
+    for i in range(len(rowptr) - 1):
+        sl = slice(int(rowptr[i]), int(rowptr[i + 1]))
+        d = dict(zip(np.asarray(colidx[sl]).tolist(), np.asarray(vals[sl]).tolist()))
+        assert len(d) == sl.stop - sl.start, "duplicate column in a row"
+        out.append(d)
+    return out
+
+
+def sell_to_rows(sellptr, cols, vals, nrows):
+    """Decode SELL-C-64 arrays (kernels.hip: element j of row s*64+lane at
+    sellptr[s] + j*64 + lane) into per-row dictionaries of the NONZERO
+    entries.  Returns (rows, entries per row incl. padding, the columns of
+    every zero-valued entry)."""
+    sellptr = np.asarray(sellptr, dtype=np.int64)
+    cols, vals = np.asarray(cols), np.asarray(vals, dtype=np.float64)
+    assert len(sellptr) - 1 == (nrows + C - 1) // C
+    assert len(cols) == len(vals) == sellptr[-1]
+    rows, lens, padcols = [], np.zeros(nrows, dtype=np.int64), []
+    for s in range(len(sellptr) - 1):
+        base, end = int(sellptr[s]), int(sellptr[s + 1])
+        assert (end - base) % C == 0
+        for lane in range(C):
+            c, v = cols[base + lane:end:C], vals[base + lane:end:C]
+            nz = v != 0.0
+            padcols.extend(c[~nz].tolist())
+            if s * C + lane >= nrows:
+                assert not nz.any(), "padding lane holds a value"
+                continue
+            d = dict(zip(c[nz].tolist(), v[nz].tolist()))
+            assert len(d) == int(nz.sum()), "duplicate column in a row"
+            rows.append(d)
+            lens[s * C + lane] = (end - base) // C
+    return rows, lens, np.asarray(padcols, dtype=np.int64)
+
+
+def rows_bits_equal(got, want):
+    """Same columns and bit-identical values in every row."""
+    if len(got) != len(want):
+        return False
+    for g, w in zip(got, want):
+        if g.keys() != w.keys():
+            return False
+        ks = sorted(w)
+        if not _bits_equal([g[k] for k in ks], [w[k] for k in ks]):
+            return False
+    return True
 
 
 # ---------------------------------------------------------------------------
@@ -442,6 +592,133 @@ def pipe_case(nowned, split, nborder0=False, short=False):
                            **vec)
 
 
+# Offset weights of the stencil cases: pairwise distinct in MAGNITUDE (so
+# w(d) != w(-d) and any exchange of two weights changes the result), not
+# dyadic, mixed signs, 0.25 <= |w| <= 2.
+_STENCIL_W = (-1.37, 0.83, -0.61, 1.19, 0.47, -1.73, 0.29, -0.97, 1.53, -0.41,
+              0.71, 1.91, -1.13, 0.37, -0.53, 1.67, -1.87, 0.59, 1.01, -0.31,
+              0.89, -1.43, 1.27, -0.67, 0.43, -1.61)
+# upper triangles (row-major) of the dense symmetric neighbour / self blocks
+_STENCIL_M = (0.77, -0.35, 0.58, 1.21, -0.49, 0.93, 0.27, 1.45, -0.63, 1.09)
+_STENCIL_D = (5.3, 0.45, -0.85, 6.1, 0.65, -0.39, 7.7, 0.55, 0.95, 4.9)
+# deliberately NOT the (-x, +x, -y, +y, -z, +z) order of the walk kernels
+_OFFS_7 = ((0, 0, 1), (-1, 0, 0), (0, 1, 0), (0, 0, -1), (1, 0, 0), (0, -1, 0))
+_OFFS_5 = ((0, 1, 0), (-1, 0, 0), (1, 0, 0), (0, -1, 0))
+_OFFS_27 = tuple((dx, dy, dz) for dz in (-1, 0, 1) for dy in (-1, 0, 1)
+                 for dx in (-1, 0, 1) if (dx, dy, dz) != (0, 0, 0))
+STENCIL_KINDS = {"7pt": (_OFFS_7, 5.3), "27pt": (_OFFS_27, 7.9),
+                 "5pt2d": (_OFFS_5, 3.7)}
+assert len(set(map(abs, _STENCIL_W))) == len(_STENCIL_W) == len(_OFFS_27)
+
+
+# (gx, gy, gz, nranks), every rank of each: a plane of 15 < one wave with an
+# uneven split whose rank 1 owns two planes, both border (ninterior = 0);
+# a plane of 63 with one plane per rank (rank 1's is both borders, two
+# ghosts); a plane of 65; gx = 1; gy = 1; serial.
+STENCIL_SHAPES_3D = ((5, 3, 7, 3), (9, 7, 3, 3), (13, 5, 7, 3), (1, 13, 4, 2),
+                     (13, 1, 5, 5), (17, 16, 6, 1))
+STENCIL_SHAPE_2D = (19, 11, 1, 1)
+# the walk kernels' grid-stride loops start above (MAXG-1024)*256 and
+# MAXG*256 = 4 194 304 columns: 2049 * 2048 = 4 196 352 is above both
+STENCIL_LARGE = ("7pt", 2049, 2048, 2, 0, 1)
+
+
+def stencil_case_ids(kinds=("7pt", "27pt")):
+    """(kind, gx, gy, gz, rank, nranks) of every rank of every shape."""
+    ids = [(k, gx, gy, gz, rank, nr) for k in kinds
+           for (gx, gy, gz, nr) in STENCIL_SHAPES_3D for rank in range(nr)]
+    return ids + [("5pt2d",) + STENCIL_SHAPE_2D[:3] + (0, 1)]
+
+
+def _sym_block(tri, dof):
+    B = np.zeros((dof, dof))
+    it = iter(tri)
+    for a in range(dof):
+        for b in range(a, dof):
+            B[a, b] = B[b, a] = next(it)
+    return B
+
+
+def stencil_spec(kind, dof=1):
+    """Stencil with per-offset weights; dof > 1: dense symmetric blocks
+    whose entries are pairwise distinct up to symmetry."""
+    offs, diag = STENCIL_KINDS[kind]
+    spec = {"offsets": [(dx, dy, dz, w) for (dx, dy, dz), w
+                        in zip(offs, _STENCIL_W)], "diag": diag, "dof": dof}
+    if dof > 1:
+        spec["offblock"] = _sym_block(_STENCIL_M, dof)
+        spec["diagblock"] = _sym_block(_STENCIL_D, dof)
+    return spec
+
+
+def stencil_case(kind, gx, gy, gz, rank, nranks, host_map=True):
+    """Rank ``rank``'s slab of a dof=1 stencil system: a global input
+    vector (SpMV input and w_old of the pipelined iteration) in local
+    order, the five owned vectors and the scalar slab of pipe_case.
+    ``host_map=False`` (serial only): local = global order, without
+    building the host slab."""
+    spec = stencil_spec(kind)
+    rng = np.random.default_rng([7000, list(STENCIL_KINDS).index(kind),
+                                 gx, gy, gz, rank, nranks])
+    plane = gx * gy
+    if host_map:
+        from acg_amd.gen.stencil import stencil_local_slab
+
+        H = stencil_local_slab(gx, gy, gz, spec, rank, nranks)
+        owned, ghost = H.owned_global, H.ghost_global
+        ninterior = H.ninterior
+    else:
+        assert nranks == 1
+        owned, ghost = np.arange(plane * gz, dtype=np.int64), np.zeros(0, np.int64)
+        ninterior = len(owned)
+    nowned, nghost = len(owned), len(ghost)
+    z0, z1 = int(owned.min()) // plane, int(owned.max()) // plane + 1
+    assert nowned == (z1 - z0) * plane
+    wg = rand_values(plane * gz, rng)
+    vec = {k: rand_values(nowned, rng) for k in "ztpxr"}
+    scal = SENTINELS.copy()
+    scal[S_GAMMA], scal[S_DELTA] = 2.3719, 3.1427
+    scal[S_GAMMA_PREV], scal[S_ALPHA_PREV] = 1.7353, 2.9131
+    return SimpleNamespace(kind=kind, spec=spec, gx=gx, gy=gy, gz=gz, rank=rank,
+                           nranks=nranks, z0=z0, z1=z1, plane=plane,
+                           owned_global=owned, ghost_global=ghost,
+                           nowned=nowned, ninterior=ninterior,
+                           nborder=nowned - ninterior, nghost=nghost,
+                           nlocal=nowned + nghost,
+                           border_base=ninterior if nghost else nowned,
+                           wg=wg, w_old=wg[np.concatenate([owned, ghost])],
+                           scal=scal, _products=None, **vec)
+
+
+def stencil_products(case):
+    """The oracle's matA part, matO part and their sum on the owned rows
+    (computed once per case): name -> (value, magnitude, products)."""
+    if case._products is None:
+        o = case.owned_global
+        args = (case.gx, case.gy, case.gz, case.spec["offsets"],
+                case.spec["diag"], case.wg)
+        A = tuple(a[o] for a in stencil_apply(*args, part=("owned", case.z0, case.z1)))
+        if case.nghost:
+            O = tuple(a[o] for a in stencil_apply(*args, part=("ghost", case.z0, case.z1)))
+            assert not O[2][:case.ninterior].any() and O[2][case.ninterior:].all()
+            full = tuple(a + b for a, b in zip(A, O))
+        else:
+            O, full = None, A
+        case._products = {"A": A, "O": O, "full": full}
+    return case._products
+
+
+def stencil_mf(case, dev):
+    """The matrix-free operator tables of the case on ``dev``, from the
+    host-side table builder (no GPU, no compiled extension needed)."""
+    from acg_amd.gen.device_slab import mf_tables_from, stencil_slab_tables
+
+    tab = stencil_slab_tables(case.gx, case.gy, case.gz, case.spec, case.rank,
+                              case.nranks)
+    return mf_tables_from(tab, tab["zs_own"].to(dev), tab["pb"].to(dev),
+                          tab["offs"].to(dev))
+
+
 def vec_case(n, pt_zero=False):
     rng = np.random.default_rng(4000 + n)
     scal = SENTINELS.copy()
@@ -575,6 +852,120 @@ def _pipelined_update(e, case, first, q, Mq, L, wo, wname):
     e.add_tol(f"scal{S_GAMMA}", g, gtol)
     e.add_tol(f"scal{S_DELTA}", d, dtol)
     e.scalars(case.scal, touched=(S_GAMMA, S_DELTA, S_GAMMA_PREV, S_ALPHA_PREV))
+
+
+def stencil_spmv_expect(case, fused, kernel="k_stencil_spmv"):
+    """matA pass (fused dot: set) and, on a rank with ghosts, the matO pass
+    over the border rows (fused dot: accumulate).  The accumulated slot is
+    the sum of two computed dots; the rounding of that one addition is
+    covered by the 8 spare roundings each dot tolerance carries."""
+    e = Expect(kernel)
+    n, ni = case.nowned, case.ninterior
+    P = stencil_products(case)
+    xo = hp(case.w_old[:n])
+    qA, MA, LA = P["A"]
+    q, M, L = P["full"]
+    tail = np.full(case.nghost, np.nan)
+    e.add("matA/y", qA, MA, LA)
+    e.add_exact("matA/y_tail", tail)
+    e.add("y", q, M, L)
+    e.add_exact("y_tail", tail)
+    e.add_same("matA/y_interior", "y_interior")
+    if fused:
+        d, tol = dot(xo, qA, tb=bound(MA, LA))
+        e.add_tol(f"matA/scal{S_PT}", d, tol)
+        if case.nborder:
+            qO, MO, LO = P["O"]
+            dO, tolO = dot(xo[ni:], qO[ni:], tb=bound(MO[ni:], LO[ni:]))
+            d, tol = d + dO, tol + tolO
+        e.add_tol(f"scal{S_PT}", d, tol)
+    for i in range(S_NSLOTS):
+        if not (fused and i == S_PT):
+            e.add_exact(f"matA/scal{i}", SENTINELS[i])
+    e.scalars(SENTINELS, touched=(S_PT,) if fused else ())
+    return e
+
+
+def stencil_pipe_expect(case, first, kernel="k_stencil_pipe"):
+    """One full megafused matrix-free iteration (matA pass, matO pass,
+    finalize) plus the state after the matA pass alone."""
+    e = Expect(kernel)
+    n, ni = case.nowned, case.ninterior
+    P = stencil_products(case)
+    q, Mq, L = P["full"]
+    _pipelined_update(e, case, first, q, Mq, L, hp(case.w_old[:n]), "w_new")
+    e.add_exact("w_new_tail", np.full(case.nghost, np.nan))
+    if case.nborder:
+        for k in "ztpxr":
+            e.add_exact(f"matA/{k}_border", getattr(case, k)[ni:])
+        e.add_exact("matA/w_new_border", np.full(case.nborder + case.nghost, np.nan))
+        qA, MA, LA = P["A"]
+        e.add("matA/qpart", qA[ni:], MA[ni:], LA[ni:])
+        e.add_same("matA/qpart", "qpart")  # the matO pass only reads it
+    else:
+        e.add_exact("qpart", np.full(1, np.nan))
+    return e
+
+
+def stencil_blocks(case, walk, n):
+    """Blocks the launchers start for an n-row pass (before the megafused
+    kernels' cap): elem_grid, or one thread per (x, y) column."""
+    return (case.plane + 255) // 256 if walk else elem_blocks(n)
+
+
+def run_stencil_spmv(ops, case, dev, mf, fused):
+    n, ni = case.nowned, case.ninterior
+    walk = mf["w7"] is not None
+    x = _t(case.w_old, dev)
+    y = _nan(case.nlocal, dev)
+    scal = _t(SENTINELS, dev)
+    partials = _nan(2 * MAXG, dev)
+    kw = dict(partials=partials, scal=scal, dotslot=S_PT) if fused else {}
+    ops.stencil_spmv(mf, n, 0, x, y, mato=False, dot_accum=False, **kw)
+    yy = _np(y)
+    got = {"matA/y": yy[:n], "matA/y_tail": yy[n:], "matA/y_interior": yy[:ni]}
+    got.update({f"matA/{k}": v for k, v in _scal_out({}, scal).items()})
+    nb = min(MAXG, stencil_blocks(case, walk, n))
+    if case.nborder:
+        ops.stencil_spmv(mf, case.nborder, ni, x, y, mato=True, dot_accum=True, **kw)
+        nb = max(nb, stencil_blocks(case, False, case.nborder))
+    yy = _np(y)
+    got.update({"y": yy[:n], "y_tail": yy[n:], "y_interior": yy[:ni]})
+    _partials_out(got, partials, nb if fused else 0)
+    return _scal_out(got, scal)
+
+
+def run_stencil_pipe(ops, case, dev, mf, first):
+    """matA pass, (matO pass with partials_off = nbA,) finalize -- the call
+    protocol of the solver."""
+    n, ni = case.nowned, case.ninterior
+    v = {k: _t(getattr(case, k), dev) for k in "ztpxr"}
+    w_old = _t(case.w_old, dev)
+    w_new = _nan(case.nlocal, dev)
+    qpart = _nan(max(case.nborder, 1), dev)
+    scal = _t(case.scal, dev)
+    partials = _nan(2 * MAXG, dev)
+    nbA = ops.stencil_pipe(mf, n, 0, case.border_base, w_old, qpart, v["z"],
+                           v["t"], v["p"], v["x"], v["r"], w_new, scal, first,
+                           partials, 0, mato=False)
+    got, nbO = {}, 0
+    if case.nborder:
+        for k in "ztpxr":
+            got[f"matA/{k}_border"] = _np(v[k][ni:])
+        got["matA/w_new_border"] = _np(w_new[ni:])
+        got["matA/qpart"] = _np(qpart)
+        nbO = ops.stencil_pipe(mf, case.nborder, ni, ni, w_old, qpart, v["z"],
+                               v["t"], v["p"], v["x"], v["r"], w_new, scal,
+                               first, partials, nbA, mato=True)
+    ops.pipelined_finalize(partials, nbA + nbO, scal, first)
+    for k in "ztpxr":
+        got[k] = _np(v[k])
+    got["qpart"] = _np(qpart)
+    got["w_new"] = _np(w_new[:n])
+    got["w_new_tail"] = _np(w_new[n:])
+    got["nbA"], got["nbO"] = int(nbA), int(nbO)
+    _partials_out(got, partials, nbA + nbO)
+    return _scal_out(got, scal)
 
 
 def fused_case(n):

@@ -220,16 +220,15 @@ def test_ref_vector_ops(n):
 
 
 def test_every_gpu_op_has_a_reference():
-    """gpu_ops and torch_ref expose the same operations (the stencil
-    generators, the monolithic device CG and host-side prep aside)."""
+    """gpu_ops and torch_ref expose the same operations (the monolithic
+    device CG and host-side prep aside)."""
     import ast
     from pathlib import Path
 
     src = Path(torch_ref.__file__).with_name("gpu_ops.py").read_text()
     ops = {n.name for n in ast.parse(src).body
            if isinstance(n, ast.FunctionDef) and not n.name.startswith("_")}
-    ops -= {"stencil_spmv", "stencil_pipe", "cg_device", "pick_lanes",
-            "build_row_bins", "build_sellcsr_hybrid"}
+    ops -= {"cg_device", "pick_lanes", "build_row_bins", "build_sellcsr_hybrid"}
     missing = sorted(o for o in ops if not hasattr(torch_ref, o))
     assert not missing, missing
 

@@ -79,6 +79,12 @@ def make_parser() -> argparse.ArgumentParser:
                         "preconditioned residual norm)")
     p.add_argument("--manufactured-solution", action="store_true",
                    help="b := A x* for random x*; report error norms")
+    p.add_argument("--nrhs", type=int, default=1, metavar="K",
+                   help="generate K right-hand sides where b is generated "
+                        "(no b file): column 0 is the single-RHS vector, "
+                        "column c > 0 is drawn from default_rng(seed + c).  "
+                        "Multiple right-hand sides (also an n x K array b "
+                        "file) need --solver acg or cpu (beyond reference)")
     p.add_argument("--numfmt", default=None, help="printf format for output values")
     p.add_argument("--output-comm-matrix", action="store_true",
                    help="print the rank x rank halo send-count matrix to "
@@ -125,6 +131,34 @@ def _vector_from_mtx(m, n: int, what: str) -> np.ndarray:
     raise AcgError(ErrCode.INVALID_FORMAT, f"{what}: unsupported format {m.format!r}")
 
 
+# solvers that accept several right-hand sides (solve_multi)
+MULTI_RHS_SOLVERS = ("acg", "cpu")
+
+
+def _rhs_from_mtx(m, n: int, what: str) -> np.ndarray:
+    """Like :func:`_vector_from_mtx`, but an ``array`` file with n rows and
+    k > 1 columns is read as k vectors: an (n, k) array (Matrix Market
+    arrays are column-major)."""
+    if m.format == "array" and m.nrows == n and m.ncols > 1:
+        vals = np.asarray(m.a, dtype=np.float64)
+        if len(vals) != n * m.ncols:
+            raise AcgError(ErrCode.INVALID_VALUE,
+                           f"{what}: {len(vals)} values for a {n}x{m.ncols} array")
+        return np.ascontiguousarray(vals.reshape(m.ncols, n).T)
+    return _vector_from_mtx(m, n, what)
+
+
+def _check_multi_rhs(k: int, solver_name: str, args) -> None:
+    if k > 1 and solver_name not in MULTI_RHS_SOLVERS:
+        raise AcgError(ErrCode.NOT_SUPPORTED,
+                       f"{k} right-hand sides are not supported by "
+                       f"{solver_name} (use acg or cpu)")
+    if k > 1 and (args.diff_atol > 0 or args.diff_rtol > 0):
+        raise AcgError(ErrCode.NOT_SUPPORTED,
+                       "--diff-atol/--diff-rtol are not supported with "
+                       "several right-hand sides")
+
+
 def main(argv=None) -> int:
     args = make_parser().parse_args(argv)
     import torch
@@ -141,6 +175,9 @@ def main(argv=None) -> int:
                    "petsc-pipelined": "scipy-pipelined"}.get(solver_name,
                                                              solver_name)
     gpu_solver = solver_name.startswith("acg")
+    if args.nrhs < 1:
+        raise AcgError(ErrCode.INVALID_VALUE, "--nrhs must be at least 1")
+    _check_multi_rhs(args.nrhs, solver_name, args)
     if gpu_solver and not has_gpu:
         print("error: GPU solver requested but no GPU is available", file=sys.stderr)
         return 1
@@ -202,6 +239,10 @@ def main(argv=None) -> int:
             n_global = A.n
 
             # RHS (reference acg-hip.c:1786-2087)
+            if args.nrhs > 1 and args.b and not args.manufactured_solution:
+                raise AcgError(ErrCode.INVALID_VALUE,
+                               "--nrhs generates right-hand sides; it cannot "
+                               "be combined with a b file")
             if args.manufactured_solution:
                 rng = np.random.default_rng(args.seed)
                 xsol = rng.standard_normal(A.n)
@@ -211,13 +252,35 @@ def main(argv=None) -> int:
                 # --binary applies to b/x0 too (reference acg-hip.c:1796)
                 mb = read_mtx(args.b, gzipped=args.gzip, binary=args.binary,
                               idxsize=args.idxsize)
-                b_global = _vector_from_mtx(mb, A.n, "b")
+                b_global = _rhs_from_mtx(mb, A.n, "b")
             else:
                 b_global = np.ones(A.n, dtype=np.float64)
+            if args.nrhs > 1:
+                # column 0 is the single-RHS vector; column c > 0 comes
+                # from default_rng(seed + c)
+                xcols, bcols = [xsol], [b_global]
+                for c in range(1, args.nrhs):
+                    v = np.random.default_rng(args.seed + c).standard_normal(A.n)
+                    if args.manufactured_solution:
+                        v /= np.linalg.norm(v)
+                        xcols.append(v)
+                        bcols.append(A.dsymv(v))
+                    else:
+                        bcols.append(v)
+                b_global = np.column_stack(bcols)
+                if args.manufactured_solution:
+                    xsol = np.column_stack(xcols)
             if args.x0:
                 mx = read_mtx(args.x0, gzipped=args.gzip, binary=args.binary,
                               idxsize=args.idxsize)
-                x0_global = _vector_from_mtx(mx, A.n, "x0")
+                x0_global = _rhs_from_mtx(mx, A.n, "x0")
+                if x0_global.shape != b_global.shape:
+                    raise AcgError(
+                        ErrCode.INVALID_VALUE,
+                        f"x0 has shape {x0_global.shape}, b has "
+                        f"{b_global.shape}: they must agree")
+            if b_global.ndim == 2:
+                _check_multi_rhs(b_global.shape[1], solver_name, args)
     except Exception as e:  # collective error agreement (acgerrmpi)
         err = e
     collective_raise(comm, err)
@@ -235,10 +298,18 @@ def main(argv=None) -> int:
             (lambda p: x0_global[ex.owned_globals[p]]) if rank == 0 else None) \
             if has_x0 else None
         n_global = comm.bcast_object(n_global)
+        nrhs = comm.bcast_object(
+            (b_global.shape[1] if b_global.ndim == 2 else 1)
+            if rank == 0 else None)
+        if nrhs > 1:  # scatter_rows carries flat (row-major) arrays
+            b_local = b_local.reshape(S.nowned, nrhs)
+            if x0_local is not None:
+                x0_local = x0_local.reshape(S.nowned, nrhs)
     else:
         S = ex.build(0)
         b_local = b_global[S.owned_global]
         x0_local = None if x0_global is None else x0_global[S.owned_global]
+        nrhs = b_global.shape[1] if b_global.ndim == 2 else 1
     log(f"scattered subdomains ({time.perf_counter() - t0:.2f}s)")
     if args.verbose and args.verbose > 1:
         S.dump(file=sys.stderr)
@@ -256,6 +327,8 @@ def main(argv=None) -> int:
         from .solvers.precond import jacobi_scale_system
 
         S, s_scale = jacobi_scale_system(S, comm, device)
+        if nrhs > 1:
+            s_scale = s_scale[:, None]  # one factor per row, every column
         b_local = b_local * s_scale
         if x0_local is not None:
             x0_local = x0_local / s_scale
@@ -276,7 +349,8 @@ def main(argv=None) -> int:
     import torch as _t
 
     b = _t.from_numpy(np.ascontiguousarray(b_local))
-    x = _t.zeros(S.nowned + S.nghost, dtype=_t.float64)
+    x = _t.zeros(S.nowned + S.nghost, dtype=_t.float64) if nrhs == 1 else \
+        _t.zeros(S.nowned + S.nghost, nrhs, dtype=_t.float64)
     if x0_local is not None:
         x[:S.nowned] = _t.from_numpy(np.ascontiguousarray(x0_local))
 
@@ -318,7 +392,14 @@ def main(argv=None) -> int:
                 raise AcgError(ErrCode.NOT_SUPPORTED,
                                f"--diff-atol/--diff-rtol are not supported "
                                f"by {solver_name} (use acg or cpu)")
-            if args.warmup:
+            if nrhs > 1:
+                if args.warmup:
+                    solver.solve_multi(b, x.clone(), maxits=args.warmup,
+                                       res_rtol=0.0)
+                res = solver.solve_multi(b, x, maxits=args.max_iterations,
+                                         res_atol=args.residual_atol,
+                                         res_rtol=args.residual_rtol)
+            elif args.warmup:
                 if solver_name == "acg-pipelined":
                     solver.solve_pipelined(b, x.clone(), maxits=args.warmup,
                                            res_rtol=0.0)
@@ -335,7 +416,9 @@ def main(argv=None) -> int:
                                         res_rtol=0.0)
                 else:
                     solver.solve(b, x.clone(), maxits=args.warmup, res_rtol=0.0)
-            if solver_name == "acg-pipelined":
+            if nrhs > 1:
+                pass  # solved above
+            elif solver_name == "acg-pipelined":
                 res = solver.solve_pipelined(b, x, maxits=args.max_iterations,
                                              res_atol=args.residual_atol,
                                              res_rtol=args.residual_rtol)
@@ -362,7 +445,11 @@ def main(argv=None) -> int:
             from .solvers.cpu import CGSolverCPU
 
             solver = CGSolverCPU(S, comm=comm)
-            if solver_name == "cpu-pipelined":
+            if nrhs > 1:
+                res = solver.solve_multi(b, x, maxits=args.max_iterations,
+                                         res_atol=args.residual_atol,
+                                         res_rtol=args.residual_rtol)
+            elif solver_name == "cpu-pipelined":
                 res = solver.solve_pipelined(b, x, maxits=args.max_iterations,
                                              res_atol=args.residual_atol,
                                              res_rtol=args.residual_rtol)
@@ -393,25 +480,32 @@ def main(argv=None) -> int:
     # ---- report (reference acgsolverhip_fwritempi, acg-hip.c:2247)
     from .solvers.profiling import write_stats
 
-    write_stats(res, S, comm, file=sys.stderr)
+    results = res if nrhs > 1 else [res]
+    for c, rc in enumerate(results):
+        if nrhs > 1 and rank == 0:
+            print(f"right-hand side {c} of {nrhs}:", file=sys.stderr)
+        write_stats(rc, S, comm, file=sys.stderr)
 
     # true-residual integrity check: ||b - A x|| of the returned iterate,
     # independent of the solver's residual recursion (bench.py computes the
     # same; silent corruption anywhere would make these diverge)
-    if res is not None:
+    for c in (range(nrhs) if res is not None else ()):
+        col = f"right-hand side {c}: " if nrhs > 1 else ""
+        bc = b if nrhs == 1 else b[:, c].contiguous()
+        xc = x if nrhs == 1 else x[:, c].contiguous()
         try:
             if gpu_solver:
                 tchk = _t.zeros(S.nowned, dtype=_t.float64, device=device)
-                solver._spmv_overlapped(x, tchk)
+                solver._spmv_overlapped(xc, tchk)
             else:
                 from .solvers.cpu import CGSolverCPU
 
                 chk = solver if isinstance(solver, CGSolverCPU) \
                     else CGSolverCPU(S, comm=comm)
                 tchk = _t.zeros(S.nowned, dtype=_t.float64)
-                chk._spmv(x, tchk)
-            rl2 = float(_t.sum((b[:S.nowned] - tchk) ** 2))
-            bl2 = float(_t.sum(b[:S.nowned] ** 2))
+                chk._spmv(xc, tchk)
+            rl2 = float(_t.sum((bc[:S.nowned] - tchk) ** 2))
+            bl2 = float(_t.sum(bc[:S.nowned] ** 2))
             if comm:
                 import torch.distributed as dist
 
@@ -421,40 +515,58 @@ def main(argv=None) -> int:
                 rl2, bl2 = float(rb[0]), float(rb[1])
             if rank == 0 and bl2 > 0:
                 lbl = " (scaled system)" if s_scale is not None else ""
-                print(f"true residual{lbl}: ||b-Ax||/||b|| = "
+                print(f"{col}true residual{lbl}: ||b-Ax||/||b|| = "
                       f"{(rl2 / bl2) ** 0.5:.6e}", file=sys.stderr)
         except Exception as e:  # side-check only: never fail the solve over it
             if rank == 0:
-                print(f"true residual: unavailable ({type(e).__name__}: {e})",
+                print(f"{col}true residual: unavailable ({type(e).__name__}: {e})",
                       file=sys.stderr)
 
     x_host = x[:S.nowned].cpu().numpy()
     if s_scale is not None:
         x_host = x_host * s_scale  # map D^1/2 x back to x
 
+    def gather_global(xl):
+        """Local rows (one vector, or one column per right-hand side) in
+        global row order on rank 0."""
+        if xl.ndim == 2:
+            cols = [gather_global(np.ascontiguousarray(xl[:, c]))
+                    for c in range(xl.shape[1])]
+            return None if cols[0] is None else np.column_stack(cols)
+        if comm:
+            return comm.gather_vector(xl, S.owned_global, n_global)
+        xg = np.empty(n_global)
+        xg[S.owned_global] = xl
+        return xg
+
     # manufactured-solution error norms (reference acg-hip.c:2354-2362)
     if args.manufactured_solution:
-        if comm:
-            xg = comm.gather_vector(x_host, S.owned_global, n_global)
-        else:
-            xg = np.empty(n_global)
-            xg[S.owned_global] = x_host
-        if rank == 0:
+        xg = gather_global(x_host)
+        if rank == 0 and nrhs == 1:
             enorm = np.linalg.norm(xg - xsol)
             print(f"manufactured solution: ||x-x*|| = {enorm:.6e} "
                   f"(||x*|| = 1)", file=sys.stderr)
+        elif rank == 0:
+            for c in range(nrhs):
+                enorm = np.linalg.norm(xg[:, c] - xsol[:, c])
+                print(f"right-hand side {c}: manufactured solution: "
+                      f"||x-x*|| = {enorm:.6e} (||x*|| = 1)", file=sys.stderr)
 
-    # solution to stdout as mtx array (reference acg-hip.c:2364-2403)
+    # solution to stdout as mtx array (reference acg-hip.c:2364-2403);
+    # several right-hand sides as one n x k array, column-major
     if not args.quiet:
-        if comm:
-            xg = comm.gather_vector(x_host, S.owned_global, n_global)
-        else:
-            xg = np.empty(n_global)
-            xg[S.owned_global] = x_host
+        xg = gather_global(x_host)
         if rank == 0:
-            from .io.mtx import vector_to_mtx, write_mtx
+            from .io.mtx import MtxFile, vector_to_mtx, write_mtx
 
-            write_mtx(sys.stdout, vector_to_mtx(xg), numfmt=numfmt)
+            if nrhs == 1:
+                out = vector_to_mtx(xg)
+            else:
+                out = MtxFile(object="matrix", format="array", field_="real",
+                              symmetry="general", nrows=n_global, ncols=nrhs,
+                              nnz=n_global * nrhs,
+                              a=np.ascontiguousarray(xg.T).reshape(-1))
+            write_mtx(sys.stdout, out, numfmt=numfmt)
     if comm:
         comm.finalize()
     # exit 2 on non-convergence whenever ANY stopping criterion was active
@@ -462,7 +574,8 @@ def main(argv=None) -> int:
     # (fixed-iteration run)
     criterion = (args.residual_rtol > 0 or args.residual_atol > 0
                  or args.diff_atol > 0 or args.diff_rtol > 0)
-    return 0 if (res is None or res.converged or not criterion) else 2
+    converged = res is None or all(rc.converged for rc in results)
+    return 0 if (converged or not criterion) else 2
 
 
 if __name__ == "__main__":

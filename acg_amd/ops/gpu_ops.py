@@ -439,6 +439,173 @@ def cg_device(sellptr: torch.Tensor, cols: torch.Tensor, vals: torch.Tensor,
                        maxits, res_atol, res_rtol, _stream(), ih)
 
 
+# ---------------------------------------------------------------------------
+# Multiple right-hand sides.  A multivector is a contiguous fp64 (n, K)
+# tensor, element (i, c) at i*K + c, K in MULTI_K at kernel level; the
+# scalar slab is (K, S_NSLOTS) and the partials scratch (K, MAXG).
+
+MULTI_K = (2, 4, 8)
+
+
+def alloc_scalars_multi(device, k: int) -> torch.Tensor:
+    return torch.zeros(k, S_NSLOTS, dtype=torch.float64, device=device)
+
+
+def alloc_partials_multi(device, k: int) -> torch.Tensor:
+    return torch.zeros(k, MAXG, dtype=torch.float64, device=device)
+
+
+def _multi_k(what: str, *mvs: torch.Tensor, rows: int | None = None) -> int:
+    """Validate multivectors (fp64, 2-D, contiguous, 16 B aligned, same K in
+    MULTI_K, at least ``rows`` rows); returns K."""
+    k = mvs[0].shape[1] if mvs[0].dim() == 2 else -1
+    if k not in MULTI_K:
+        raise ValueError(f"{what}: multivectors must have shape (n, K) with K "
+                         f"in {MULTI_K}, got {tuple(mvs[0].shape)}")
+    for v in mvs:
+        if v.dtype != torch.float64:
+            raise TypeError(f"{what}: multivectors must be float64, got {v.dtype}")
+        if v.dim() != 2 or v.shape[1] != k:
+            raise ValueError(f"{what}: multivector shapes disagree: "
+                             f"{[tuple(m.shape) for m in mvs]}")
+        if not v.is_contiguous():
+            raise ValueError(f"{what}: multivectors must be contiguous")
+        if v.data_ptr() % 16:
+            raise ValueError(f"{what}: multivectors must be 16-byte aligned")
+        if rows is not None and v.shape[0] < rows:
+            raise ValueError(f"{what}: multivector has {v.shape[0]} rows, "
+                             f"needs at least {rows}")
+    return k
+
+
+def _multi_slab(what: str, k: int, scal: torch.Tensor,
+                partials: torch.Tensor | None) -> None:
+    for t, cols, nm in ((scal, S_NSLOTS, "scal"), (partials, MAXG, "partials")):
+        if t is None:
+            continue
+        if (t.dtype != torch.float64 or not t.is_contiguous()
+                or t.numel() < k * cols):
+            raise ValueError(f"{what}: {nm} must be a contiguous float64 "
+                             f"({k}, {cols}) tensor")
+
+
+def spmm_bsell_supported(dof: int, k: int) -> bool:
+    """True where a register-resident k_spmm_bsell<dof, k> exists."""
+    return bool(K.spmm_bsell_supported(dof, k))
+
+
+def spmm_sell(sellptr: torch.Tensor, cols: torch.Tensor, vals: torch.Tensor,
+              nrows: int, X: torch.Tensor, Y: torch.Tensor, *,
+              partials: torch.Tensor | None = None,
+              scal: torch.Tensor | None = None, dotslot: int = -1,
+              dot_accum: bool = False,
+              perm: torch.Tensor | None = None) -> None:
+    """SELL-C-64(-sigma) SpMM: Y[:nrows] = A X for K interleaved vectors;
+    optional fused per-column dot (X_c, Y_c) into slot ``dotslot`` of every
+    column's slab.  fp64 operator values only."""
+    k = _multi_k("spmm_sell", X, Y, rows=nrows)
+    if vals.dtype != torch.float64:
+        raise TypeError(f"spmm_sell: operator values must be float64, got {vals.dtype}")
+    if cols.dtype not in (torch.int32, torch.int64):
+        raise TypeError(f"spmm_sell: cols must be int32 or int64, got {cols.dtype}")
+    if perm is not None and perm.dtype != torch.int32:
+        raise TypeError("spmm_sell: perm must be int32")
+    nslices = sellptr.numel() - 1
+    if nslices <= 0:
+        return
+    fuse = scal is not None and dotslot >= 0
+    if fuse:
+        _multi_slab("spmm_sell", k, scal, partials)
+    K.spmm_sell(nslices, nrows, k, sellptr.data_ptr(), cols.data_ptr(),
+                1 if cols.dtype == torch.int64 else 0, vals.data_ptr(),
+                X.data_ptr(), Y.data_ptr(),
+                partials.data_ptr() if fuse else 0,
+                scal.data_ptr() if fuse else 0, dotslot, dot_accum,
+                perm.data_ptr() if perm is not None else 0, _stream())
+
+
+def spmm_bsell(bptr: torch.Tensor, bcol: torch.Tensor, bvals: torch.Tensor,
+               nnodes: int, dof: int, X: torch.Tensor, Y: torch.Tensor, *,
+               partials: torch.Tensor | None = None,
+               scal: torch.Tensor | None = None, dotslot: int = -1,
+               dot_accum: bool = False) -> None:
+    """Block-SELL SpMM (dof in 2/3/4), same fused dot as :func:`spmm_sell`."""
+    k = _multi_k("spmm_bsell", X, Y, rows=nnodes * dof)
+    if bvals.dtype != torch.float64:
+        raise TypeError(f"spmm_bsell: operator values must be float64, got {bvals.dtype}")
+    if not spmm_bsell_supported(dof, k):
+        raise ValueError(f"spmm_bsell: no kernel for dof={dof}, K={k}")
+    nslices = bptr.numel() - 1
+    if nslices <= 0:
+        return
+    fuse = scal is not None and dotslot >= 0
+    if fuse:
+        _multi_slab("spmm_bsell", k, scal, partials)
+    K.spmm_bsell(nslices, nnodes, dof, k, bptr.data_ptr(), bcol.data_ptr(),
+                 bvals.data_ptr(), X.data_ptr(), Y.data_ptr(),
+                 partials.data_ptr() if fuse else 0,
+                 scal.data_ptr() if fuse else 0, dotslot, dot_accum, _stream())
+
+
+def dot_multi(X: torch.Tensor, Y: torch.Tensor, partials: torch.Tensor,
+              scal: torch.Tensor, slot: int, n: int | None = None,
+              accumulate: bool = False) -> None:
+    """scal[c, slot] (=|+=) (X[:n, c], Y[:n, c]) for every column c."""
+    n = X.shape[0] if n is None else n
+    k = _multi_k("dot_multi", X, Y, rows=n)
+    _multi_slab("dot_multi", k, scal, partials)
+    K.dot_multi(X.data_ptr(), Y.data_ptr(), n, k, partials.data_ptr(),
+                scal.data_ptr(), slot, accumulate, _stream())
+
+
+def reduce_partials_multi(partials: torch.Tensor, nblocks: int,
+                          scal: torch.Tensor, slot: int,
+                          accumulate: bool = False) -> None:
+    """scal[c, slot] (=|+=) sum(partials[c, :nblocks]) for every column."""
+    k = scal.numel() // S_NSLOTS
+    _multi_slab("reduce_partials_multi", k, scal, partials)
+    K.reduce_partials_multi(partials.data_ptr(), nblocks, k, scal.data_ptr(),
+                            slot, accumulate, _stream())
+
+
+def cg_fused_update_multi(R: torch.Tensor, X: torch.Tensor, P: torch.Tensor,
+                          T: torch.Tensor, scal: torch.Tensor,
+                          partials: torch.Tensor, n: int) -> int:
+    """Per column c: alpha_c = scal[c, RR]/scal[c, PT]; R -= alpha_c T;
+    X += alpha_c P on the first n rows.  Leaves the block partials of the
+    new (r, r) in ``partials[c, :nblocks]`` for :func:`cg_finalize_multi`
+    and returns nblocks."""
+    k = _multi_k("cg_fused_update_multi", R, X, P, T, rows=n)
+    _multi_slab("cg_fused_update_multi", k, scal, partials)
+    return int(K.cg_fused_update_multi(R.data_ptr(), X.data_ptr(), P.data_ptr(),
+                                       T.data_ptr(), n, k, scal.data_ptr(),
+                                       partials.data_ptr(), _stream()))
+
+
+def cg_finalize_multi(partials: torch.Tensor, nblocks: int, scal: torch.Tensor,
+                      rr_out: torch.Tensor) -> None:
+    """Per column c: rotate RR -> RR_PREV, publish sum(partials[c, :nblocks])
+    as the new RR and as ``rr_out[c]`` (contiguous, for the host test)."""
+    k = scal.numel() // S_NSLOTS
+    _multi_slab("cg_finalize_multi", k, scal, partials)
+    if (rr_out.dtype != torch.float64 or not rr_out.is_contiguous()
+            or rr_out.numel() < k):
+        raise ValueError(f"cg_finalize_multi: rr_out must be float64[{k}]")
+    K.cg_finalize_multi(partials.data_ptr(), nblocks, k, scal.data_ptr(),
+                        rr_out.data_ptr(), _stream())
+
+
+def daypx_ratio_multi(P: torch.Tensor, R: torch.Tensor, scal: torch.Tensor,
+                      num: int = S_RR, den: int = S_RR_PREV,
+                      n: int | None = None) -> None:
+    """P[:n, c] = (scal[c, num]/scal[c, den]) P[:n, c] + R[:n, c]."""
+    n = R.shape[0] if n is None else n
+    k = _multi_k("daypx_ratio_multi", P, R, rows=n)
+    _multi_slab("daypx_ratio_multi", k, scal, None)
+    K.daypx_ratio_multi(P.data_ptr(), R.data_ptr(), n, k, scal.data_ptr(),
+                        num, den, _stream())
+
+
 def pack_gather(sendbuf: torch.Tensor, x: torch.Tensor, idx: torch.Tensor) -> None:
     K.pack_gather(sendbuf.data_ptr(), x.data_ptr(), idx.data_ptr(),
                   1 if idx.dtype == torch.int64 else 0,

@@ -27,7 +27,11 @@
 //      launch) with a hand-rolled agent-scope grid barrier (sc1
 //      write-through payloads, per-XCD generation lines, parity counters,
 //      bounded spins -- cooperative grid.sync measured ~150 us/sync),
-//   6. halo pack gather (no unpack exists: ghosts are received in place).
+//   6. halo pack gather (no unpack exists: ghosts are received in place),
+//   7. multiple right-hand sides: SELL / BSELL SpMM over K = 2, 4, 8
+//      interleaved vectors (each matrix value and index read once for K
+//      products) and the per-column dot / fused update / finalize / daypx
+//      kernels of the batched classic CG.
 //
 // The scalar slab layout (fp64 slots) is shared with solvers/hip.py:
 #define S_RR 0         // (r,r) current
@@ -1702,6 +1706,326 @@ k_pack_gather(double* __restrict__ sendbuf, const double* __restrict__ x,
 }
 
 // ---------------------------------------------------------------------------
+// Multiple right-hand sides.  A multivector is a contiguous (n, K) fp64
+// array, K in {2, 4, 8}: element (i, c) at i*K + c, ghost rows as the
+// tail.  The K values of a row are one 16*K/2-byte run, so every gather
+// of the operator kernels below is K/2 dwordx4 loads from ONE address
+// (K = 8 uses half of a 128 B line instead of 8 B of it), and each matrix
+// value / column index is read once for K products.  Scalars: column c
+// owns the 8-slot slab at scal + c*S_NSLOTS and the partials range
+// [c*MAXG, c*MAXG + gridDim.x).  fp64 operator values only.
+typedef double d2_t __attribute__((ext_vector_type(2)));
+
+template <int K>
+__device__ __forceinline__ void ld_row(const double* __restrict__ p, double (&v)[K]) {
+    const d2_t* __restrict__ q = (const d2_t*)p;
+    #pragma unroll
+    for (int h = 0; h < K / 2; ++h) {
+        const d2_t w = q[h];
+        v[2 * h] = w.x;
+        v[2 * h + 1] = w.y;
+    }
+}
+
+template <int K>
+__device__ __forceinline__ void st_row(double* __restrict__ p, const double (&v)[K]) {
+    d2_t* __restrict__ q = (d2_t*)p;
+    #pragma unroll
+    for (int h = 0; h < K / 2; ++h) {
+        d2_t w;
+        w.x = v[2 * h];
+        w.y = v[2 * h + 1];
+        q[h] = w;
+    }
+}
+
+// K block sums -> partials[c*MAXG + blockIdx.x]
+template <int K>
+__device__ __forceinline__ void block_reduce_cols(const double (&d)[K],
+                                                  double* __restrict__ partials) {
+    #pragma unroll
+    for (int c = 0; c < K; ++c) {
+        if (c) __syncthreads();  // block_reduce reuses its LDS scratch
+        const double v = block_reduce(d[c]);
+        if (threadIdx.x == 0) partials[(long)c * MAXG + blockIdx.x] = v;
+    }
+}
+
+// SELL-C-64 SpMM: Y = A X for K interleaved vectors.  Same arrays as
+// k_spmv_sell; lane = row, vals/cols NT (read once).  Unroll depth U: the
+// single-vector kernel keeps 8 gathers of 8 B in flight per lane; here a
+// gather is K/2 dwordx4 loads, so U = 4 (K = 2) or 2 (K = 4, 8) keeps
+// 4..8 16-byte loads in flight while a[U] + xx[U][K] + acc[K] stay well
+// inside the register file (no scratch, see profiles/multi_rhs.md).
+template <typename ColT, int K, bool FUSE_DOT, bool PERM>
+__global__ void __launch_bounds__(BLOCK)
+k_spmm_sell(long nslices, long nrows,
+            const long* __restrict__ sellptr,
+            const ColT* __restrict__ cols,
+            const double* __restrict__ vals,
+            const double* __restrict__ X,
+            double* __restrict__ Y,
+            double* __restrict__ partials,
+            const int* __restrict__ perm) {
+    constexpr int U = (K == 2) ? 4 : 2;
+    const int lane = threadIdx.x & (WAVE - 1);
+    const long wslice = ((long)blockIdx.x * BLOCK + threadIdx.x) >> 6;
+    const long nw = ((long)gridDim.x * BLOCK) >> 6;
+    double dacc[K];
+    #pragma unroll
+    for (int c = 0; c < K; ++c) dacc[c] = 0.0;
+    for (long s = wslice; s < nslices; s += nw) {
+        const long base = sellptr[s];
+        const long len = (sellptr[s + 1] - base) >> 6;
+        const double* __restrict__ v = vals + base + lane;
+        const ColT* __restrict__ cp = cols + base + lane;
+        double acc[K];
+        #pragma unroll
+        for (int c = 0; c < K; ++c) acc[c] = 0.0;
+        long j = 0;
+        for (; j + U <= len; j += U) {
+            double a[U], xx[U][K];
+            #pragma unroll
+            for (int u = 0; u < U; ++u) {
+                a[u] = ld_nt(v + (j + u) * WAVE);
+                const long ci = (long)ld_nt(cp + (j + u) * WAVE);
+                ld_row<K>(X + ci * K, xx[u]);
+            }
+            #pragma unroll
+            for (int u = 0; u < U; ++u) {
+                #pragma unroll
+                for (int c = 0; c < K; ++c) acc[c] += a[u] * xx[u][c];
+            }
+        }
+        for (; j < len; ++j) {
+            const double a = ld_nt(v + j * WAVE);
+            const long ci = (long)ld_nt(cp + j * WAVE);
+            double xx[K];
+            ld_row<K>(X + ci * K, xx);
+            #pragma unroll
+            for (int c = 0; c < K; ++c) acc[c] += a * xx[c];
+        }
+        const long row = PERM ? (long)perm[s * WAVE + lane] : s * WAVE + lane;
+        if (row < nrows) {
+            st_row<K>(Y + row * K, acc);
+            if (FUSE_DOT) {
+                double xr[K];
+                ld_row<K>(X + row * K, xr);
+                #pragma unroll
+                for (int c = 0; c < K; ++c) dacc[c] += xr[c] * acc[c];
+            }
+        }
+    }
+    if (FUSE_DOT) block_reduce_cols<K>(dacc, partials);
+}
+
+// Block-SELL SpMM: the DOF^2 values of a block are loaded once and applied
+// to the DOF x K gathered values (one contiguous DOF*K*8-byte run at
+// X + cb*DOF*K), acc[DOF][K] in registers.
+template <int DOF, int K, bool FUSE_DOT>
+__global__ void __launch_bounds__(BLOCK)
+k_spmm_bsell(long nslices, long nnodes,
+             const long* __restrict__ bptr,
+             const int* __restrict__ bcol,
+             const double* __restrict__ bvals,
+             const double* __restrict__ X,
+             double* __restrict__ Y,
+             double* __restrict__ partials) {
+    const int lane = threadIdx.x & (WAVE - 1);
+    const long wslice = ((long)blockIdx.x * BLOCK + threadIdx.x) >> 6;
+    const long nw = ((long)gridDim.x * BLOCK) >> 6;
+    double dacc[K];
+    #pragma unroll
+    for (int c = 0; c < K; ++c) dacc[c] = 0.0;
+    for (long s = wslice; s < nslices; s += nw) {
+        const long b0 = bptr[s];
+        const long blen = (bptr[s + 1] - b0) >> 6;
+        const int* __restrict__ cp = bcol + b0 + lane;
+        const double* __restrict__ v = bvals + b0 * (DOF * DOF);
+        double acc[DOF][K];
+        #pragma unroll
+        for (int r = 0; r < DOF; ++r) {
+            #pragma unroll
+            for (int c = 0; c < K; ++c) acc[r][c] = 0.0;
+        }
+        for (long j = 0; j < blen; ++j) {
+            const long cb = (long)ld_nt(cp + j * WAVE);
+            const double* __restrict__ xb = X + cb * (DOF * K);
+            const double* __restrict__ vj = v + j * (DOF * DOF) * WAVE;
+            double a[DOF * DOF];
+            #pragma unroll
+            for (int k = 0; k < DOF * DOF; ++k)
+                a[k] = ld_nt(vj + bval_off<DOF * DOF>(k, lane));
+            #pragma unroll
+            for (int cc = 0; cc < DOF; ++cc) {
+                double xv[K];
+                ld_row<K>(xb + cc * K, xv);
+                #pragma unroll
+                for (int r = 0; r < DOF; ++r) {
+                    #pragma unroll
+                    for (int c = 0; c < K; ++c) acc[r][c] += a[r * DOF + cc] * xv[c];
+                }
+            }
+        }
+        const long node = s * WAVE + lane;
+        if (node < nnodes) {
+            #pragma unroll
+            for (int r = 0; r < DOF; ++r) {
+                st_row<K>(Y + (node * DOF + r) * K, acc[r]);
+                if (FUSE_DOT) {
+                    double xr[K];
+                    ld_row<K>(X + (node * DOF + r) * K, xr);
+                    #pragma unroll
+                    for (int c = 0; c < K; ++c) dacc[c] += xr[c] * acc[r][c];
+                }
+            }
+        }
+    }
+    if (FUSE_DOT) block_reduce_cols<K>(dacc, partials);
+}
+
+// Element-wise multi kernels: FLAT mapping.  A thread owns one 16-byte
+// pair (i, c), (i, c+1) per grid stride, so a wave instruction covers one
+// contiguous 1 KB run whatever K is.  (One thread per whole row was
+// measured first: at K = 8 every dwordx4 instruction then strides 64 B
+// across the lanes and the fused update ran at 2.6 TB/s, 604 us against
+// 8 x 38 us for the single-vector kernel at 4.1 M rows.)  The grid stride
+// is a multiple of K/2 pairs, so a thread keeps the same column pair
+// h = threadIdx.x % (K/2) for its whole life and needs two coefficients.
+//
+// pair_reduce_cols: per-column block sums of the threads' (column 2h,
+// column 2h+1) accumulators.  The wave tree stops at offset K/2, which
+// leaves lane l < K/2 with the sum over its residue class; the 4 wave
+// results meet in LDS and thread c < K publishes column c.
+template <int K>
+__device__ __forceinline__ void pair_reduce_cols(double a0, double a1,
+                                                 double* __restrict__ partials) {
+    constexpr int H = K / 2;
+    #pragma unroll
+    for (int off = WAVE / 2; off >= H; off >>= 1) {
+        a0 += __shfl_down(a0, off, WAVE);
+        a1 += __shfl_down(a1, off, WAVE);
+    }
+    __shared__ double w[BLOCK / WAVE][K];
+    const int lane = threadIdx.x & (WAVE - 1);
+    const int wid = threadIdx.x >> 6;
+    if (lane < H) {
+        w[wid][2 * lane] = a0;
+        w[wid][2 * lane + 1] = a1;
+    }
+    __syncthreads();
+    if (threadIdx.x < K) {
+        double v = 0.0;
+        #pragma unroll
+        for (int q = 0; q < BLOCK / WAVE; ++q) v += w[q][threadIdx.x];
+        partials[(long)threadIdx.x * MAXG + blockIdx.x] = v;
+    }
+}
+
+// per-column dots of two (n, K) multivectors; npairs = n*K/2
+template <int K>
+__global__ void __launch_bounds__(BLOCK)
+k_dot_multi(const double* __restrict__ X, const double* __restrict__ Y,
+            long npairs, double* __restrict__ partials) {
+    const d2_t* __restrict__ xp = (const d2_t*)X;
+    const d2_t* __restrict__ yp = (const d2_t*)Y;
+    double a0 = 0.0, a1 = 0.0;
+    const long stride = (long)gridDim.x * BLOCK;
+    for (long i = (long)blockIdx.x * BLOCK + threadIdx.x; i < npairs; i += stride) {
+        const d2_t xv = xp[i], yv = yp[i];
+        a0 += xv.x * yv.x;
+        a1 += xv.y * yv.y;
+    }
+    pair_reduce_cols<K>(a0, a1, partials);
+}
+
+// grid = K blocks: block c sums column c's partials into slot `slot` of
+// column c's slab
+__global__ void __launch_bounds__(BLOCK)
+k_reduce_partials_multi(const double* __restrict__ partials, int nblocks,
+                        double* scal, int slot, int accumulate) {
+    const double* __restrict__ pc = partials + (long)blockIdx.x * MAXG;
+    double* sc = scal + (long)blockIdx.x * S_NSLOTS;
+    double v = 0.0;
+    for (int i = threadIdx.x; i < nblocks; i += BLOCK) v += pc[i];
+    v = block_reduce(v);
+    if (threadIdx.x == 0) sc[slot] = accumulate ? sc[slot] + v : v;
+}
+
+// classic-CG fused update for K columns: alpha_c = rr_c/pt_c from column
+// c's slab; R -= alpha_c T; X += alpha_c P; K partials of the new (r,r).
+// Same NT discipline as k_cg_fused_update (T and X single-use streams).
+template <int K>
+__global__ void __launch_bounds__(BLOCK)
+k_cg_fused_update_multi(double* __restrict__ R, double* __restrict__ X,
+                        const double* __restrict__ P, const double* __restrict__ T,
+                        long npairs, const double* __restrict__ scal,
+                        double* __restrict__ partials) {
+    const int c0 = 2 * (threadIdx.x % (K / 2));
+    const double al0 = safe_div(scal[c0 * S_NSLOTS + S_RR], scal[c0 * S_NSLOTS + S_PT]);
+    const double al1 = safe_div(scal[(c0 + 1) * S_NSLOTS + S_RR],
+                                scal[(c0 + 1) * S_NSLOTS + S_PT]);
+    d2_t* __restrict__ rp = (d2_t*)R;
+    d2_t* __restrict__ xp = (d2_t*)X;
+    const d2_t* __restrict__ pp = (const d2_t*)P;
+    const d2_t* __restrict__ tp = (const d2_t*)T;
+    double a0 = 0.0, a1 = 0.0;
+    const long stride = (long)gridDim.x * BLOCK;
+    for (long i = (long)blockIdx.x * BLOCK + threadIdx.x; i < npairs; i += stride) {
+        d2_t rv = rp[i], xv = ld_nt(xp + i);
+        const d2_t tv = ld_nt(tp + i), pv = pp[i];
+        rv.x = rv.x - al0 * tv.x;
+        rv.y = rv.y - al1 * tv.y;
+        xv.x = xv.x + al0 * pv.x;
+        xv.y = xv.y + al1 * pv.y;
+        rp[i] = rv;
+        __builtin_nontemporal_store(xv, xp + i);
+        a0 += rv.x * rv.x;
+        a1 += rv.y * rv.y;
+    }
+    pair_reduce_cols<K>(a0, a1, partials);
+}
+
+// grid = K blocks: block c rotates rr -> rr_prev in column c's slab,
+// publishes the new (r,r) there AND in the contiguous rr_out[c] (the host
+// convergence test stays one small D2H copy per iteration)
+__global__ void __launch_bounds__(BLOCK)
+k_cg_finalize_multi(const double* __restrict__ partials, int nblocks,
+                    double* scal, double* __restrict__ rr_out) {
+    const double* __restrict__ pc = partials + (long)blockIdx.x * MAXG;
+    double* sc = scal + (long)blockIdx.x * S_NSLOTS;
+    double v = 0.0;
+    for (int i = threadIdx.x; i < nblocks; i += BLOCK) v += pc[i];
+    v = block_reduce(v);
+    if (threadIdx.x == 0) {
+        sc[S_RR_PREV] = sc[S_RR];
+        sc[S_RR] = v;
+        rr_out[blockIdx.x] = v;
+    }
+}
+
+// P = beta_c P + R with beta_c = scal[c][num]/scal[c][den]
+template <int K>
+__global__ void __launch_bounds__(BLOCK)
+k_daypx_ratio_multi(double* __restrict__ P, const double* __restrict__ R,
+                    long npairs, const double* __restrict__ scal, int num, int den) {
+    const int c0 = 2 * (threadIdx.x % (K / 2));
+    const double b0 = safe_div(scal[c0 * S_NSLOTS + num], scal[c0 * S_NSLOTS + den]);
+    const double b1 = safe_div(scal[(c0 + 1) * S_NSLOTS + num],
+                               scal[(c0 + 1) * S_NSLOTS + den]);
+    d2_t* __restrict__ pp = (d2_t*)P;
+    const d2_t* __restrict__ rp = (const d2_t*)R;
+    const long stride = (long)gridDim.x * BLOCK;
+    for (long i = (long)blockIdx.x * BLOCK + threadIdx.x; i < npairs; i += stride) {
+        d2_t pv = pp[i];
+        const d2_t rv = rp[i];
+        pv.x = b0 * pv.x + rv.x;
+        pv.y = b1 * pv.y + rv.y;
+        pp[i] = pv;
+    }
+}
+
+// ---------------------------------------------------------------------------
 // host-side launchers (pybind).  Tensors arrive as raw device pointers +
 // sizes + the caller's HIP stream handle (torch.cuda.current_stream().cuda_stream);
 // no torch C++ dependency, no hipify, plain HIP throughout.
@@ -2100,8 +2424,156 @@ void pack_gather(uintptr_t sendbuf, uintptr_t x, uintptr_t idx, int idx64, long 
     check_hip("pack_gather");
 }
 
+// -- multiple right-hand sides ------------------------------------------------
+
+#define DISPATCH_K(k, WHAT, MACRO) \
+    switch (k) { \
+        case 2: MACRO(2); break; \
+        case 4: MACRO(4); break; \
+        case 8: MACRO(8); break; \
+        default: throw std::invalid_argument(WHAT ": K must be 2, 4 or 8"); }
+
+void reduce_partials_multi(uintptr_t partials, int nblocks, int k, uintptr_t scal,
+                           int slot, bool accumulate, uintptr_t stream) {
+    if (k < 1 || k > 8) throw std::invalid_argument("reduce_partials_multi: K must be 1..8");
+    if (nblocks < 0 || nblocks > MAXG || slot < 0 || slot >= S_NSLOTS)
+        throw std::invalid_argument("reduce_partials_multi: nblocks/slot out of range");
+    hipLaunchKernelGGL(k_reduce_partials_multi, dim3((unsigned)k), dim3(BLOCK), 0,
+                       S(stream), (const double*)partials, nblocks, (double*)scal,
+                       slot, accumulate ? 1 : 0);
+    check_hip("reduce_partials_multi");
+}
+
+long spmm_sell(long nslices, long nrows, int k, uintptr_t sellptr, uintptr_t cols,
+               int col64, uintptr_t vals, uintptr_t X, uintptr_t Y,
+               uintptr_t partials, uintptr_t scal, int dotslot, bool dot_accum,
+               uintptr_t perm, uintptr_t stream) {
+    if (nrows == 0 || nslices == 0) return 0;
+    long blocks = (nslices * WAVE + BLOCK - 1) / BLOCK;
+    if (blocks > MAXG) blocks = MAXG;
+    const bool fuse = partials != 0 && dotslot >= 0;
+    dim3 g((unsigned)blocks), b(BLOCK);
+    #define LAUNCH_SPMM(CT, KK, FD, PM) \
+        hipLaunchKernelGGL((k_spmm_sell<CT, KK, FD, PM>), g, b, 0, S(stream), \
+            nslices, nrows, (const long*)sellptr, (const CT*)cols, \
+            (const double*)vals, (const double*)X, (double*)Y, \
+            (double*)partials, (const int*)perm)
+    #define SPMM_PM(CT, KK, FD) \
+        if (perm != 0) { LAUNCH_SPMM(CT, KK, FD, true); } else { LAUNCH_SPMM(CT, KK, FD, false); }
+    #define SPMM_K(KK) \
+        if (col64) { if (fuse) { SPMM_PM(long, KK, true) } else { SPMM_PM(long, KK, false) } } \
+        else       { if (fuse) { SPMM_PM(int, KK, true) } else { SPMM_PM(int, KK, false) } }
+    DISPATCH_K(k, "spmm_sell", SPMM_K)
+    #undef SPMM_K
+    #undef SPMM_PM
+    #undef LAUNCH_SPMM
+    check_hip("spmm_sell");
+    if (fuse)
+        reduce_partials_multi(partials, (int)blocks, k, scal, dotslot, dot_accum, stream);
+    return blocks;
+}
+
+// (dof, K) pairs with a register-resident instantiation; none spills, so
+// every pair is offered (see profiles/multi_rhs.md for the table)
+bool spmm_bsell_supported(int dof, int k) {
+    return dof >= 2 && dof <= 4 && (k == 2 || k == 4 || k == 8);
+}
+
+long spmm_bsell(long nslices, long nnodes, int dof, int k, uintptr_t bptr,
+                uintptr_t bcol, uintptr_t bvals, uintptr_t X, uintptr_t Y,
+                uintptr_t partials, uintptr_t scal, int dotslot, bool dot_accum,
+                uintptr_t stream) {
+    if (!spmm_bsell_supported(dof, k))
+        throw std::invalid_argument("spmm_bsell: dof must be 2/3/4 and K 2/4/8");
+    if (nnodes == 0 || nslices == 0) return 0;
+    long blocks = (nslices * WAVE + BLOCK - 1) / BLOCK;
+    if (blocks > MAXG) blocks = MAXG;
+    const bool fuse = partials != 0 && dotslot >= 0;
+    dim3 g((unsigned)blocks), b(BLOCK);
+    #define LAUNCH_BSPMM(D, KK, FD) \
+        hipLaunchKernelGGL((k_spmm_bsell<D, KK, FD>), g, b, 0, S(stream), \
+            nslices, nnodes, (const long*)bptr, (const int*)bcol, \
+            (const double*)bvals, (const double*)X, (double*)Y, (double*)partials)
+    #define BSPMM_K(KK) \
+        switch (dof) { \
+            case 2: if (fuse) { LAUNCH_BSPMM(2, KK, true); } else { LAUNCH_BSPMM(2, KK, false); } break; \
+            case 3: if (fuse) { LAUNCH_BSPMM(3, KK, true); } else { LAUNCH_BSPMM(3, KK, false); } break; \
+            default: if (fuse) { LAUNCH_BSPMM(4, KK, true); } else { LAUNCH_BSPMM(4, KK, false); } break; }
+    DISPATCH_K(k, "spmm_bsell", BSPMM_K)
+    #undef BSPMM_K
+    #undef LAUNCH_BSPMM
+    check_hip("spmm_bsell");
+    if (fuse)
+        reduce_partials_multi(partials, (int)blocks, k, scal, dotslot, dot_accum, stream);
+    return blocks;
+}
+
+long dot_multi(uintptr_t X, uintptr_t Y, long n, int k, uintptr_t partials,
+               uintptr_t scal, int slot, bool accumulate, uintptr_t stream) {
+    const long blocks = elem_grid(n * k / 2, 1);
+    dim3 g((unsigned)blocks), b(BLOCK);
+    #define DOT_K(KK) \
+        hipLaunchKernelGGL(k_dot_multi<KK>, g, b, 0, S(stream), (const double*)X, \
+                           (const double*)Y, n * KK / 2, (double*)partials)
+    DISPATCH_K(k, "dot_multi", DOT_K)
+    #undef DOT_K
+    check_hip("dot_multi");
+    reduce_partials_multi(partials, (int)blocks, k, scal, slot, accumulate, stream);
+    return blocks;
+}
+
+// update only: the K partial sets stay in `partials` for cg_finalize_multi;
+// returns the number of blocks (= partials per column)
+long cg_fused_update_multi(uintptr_t R, uintptr_t X, uintptr_t P, uintptr_t T,
+                           long n, int k, uintptr_t scal, uintptr_t partials,
+                           uintptr_t stream) {
+    const long blocks = elem_grid(n * k / 2, 1);
+    dim3 g((unsigned)blocks), b(BLOCK);
+    #define UPD_K(KK) \
+        hipLaunchKernelGGL(k_cg_fused_update_multi<KK>, g, b, 0, S(stream), \
+                           (double*)R, (double*)X, (const double*)P, (const double*)T, \
+                           n * KK / 2, (const double*)scal, (double*)partials)
+    DISPATCH_K(k, "cg_fused_update_multi", UPD_K)
+    #undef UPD_K
+    check_hip("cg_fused_update_multi");
+    return blocks;
+}
+
+void cg_finalize_multi(uintptr_t partials, int nblocks, int k, uintptr_t scal,
+                       uintptr_t rr_out, uintptr_t stream) {
+    if (k < 1 || k > 8) throw std::invalid_argument("cg_finalize_multi: K must be 1..8");
+    if (nblocks < 0 || nblocks > MAXG)
+        throw std::invalid_argument("cg_finalize_multi: nblocks out of range");
+    hipLaunchKernelGGL(k_cg_finalize_multi, dim3((unsigned)k), dim3(BLOCK), 0,
+                       S(stream), (const double*)partials, nblocks, (double*)scal,
+                       (double*)rr_out);
+    check_hip("cg_finalize_multi");
+}
+
+void daypx_ratio_multi(uintptr_t P, uintptr_t R, long n, int k, uintptr_t scal,
+                       int num, int den, uintptr_t stream) {
+    if (num < 0 || num >= S_NSLOTS || den < 0 || den >= S_NSLOTS)
+        throw std::invalid_argument("daypx_ratio_multi: slot out of range");
+    dim3 g((unsigned)elem_grid(n * k / 2, 1)), b(BLOCK);
+    #define DAYPX_K(KK) \
+        hipLaunchKernelGGL(k_daypx_ratio_multi<KK>, g, b, 0, S(stream), (double*)P, \
+                           (const double*)R, n * KK / 2, (const double*)scal, num, den)
+    DISPATCH_K(k, "daypx_ratio_multi", DAYPX_K)
+    #undef DAYPX_K
+    check_hip("daypx_ratio_multi");
+}
+#undef DISPATCH_K
+
 PYBIND11_MODULE(_acg_kernels, m) {
     m.doc() = "acg_amd gfx950 HIP kernels";
+    m.def("spmm_sell", &spmm_sell);
+    m.def("spmm_bsell", &spmm_bsell);
+    m.def("spmm_bsell_supported", &spmm_bsell_supported);
+    m.def("dot_multi", &dot_multi);
+    m.def("reduce_partials_multi", &reduce_partials_multi);
+    m.def("cg_fused_update_multi", &cg_fused_update_multi);
+    m.def("cg_finalize_multi", &cg_finalize_multi);
+    m.def("daypx_ratio_multi", &daypx_ratio_multi);
     m.def("spmv", &spmv);
     m.def("spmv_binned", &spmv_binned);
     m.def("spmv_sell", &spmv_sell);

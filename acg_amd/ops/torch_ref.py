@@ -627,5 +627,132 @@ def pipelined_finalize(partials, nblocks: int, scal, first: bool) -> None:
     scal[S_DELTA] = d
 
 
+# ---------------------------------------------------------------------------
+# Multiple right-hand sides (same layout as gpu_ops: (n, K) multivectors,
+# (K, S_NSLOTS) slab, (K, MAXG) partials).  Every column is computed by the
+# single-vector reference above, so a column of a multi op IS the single op.
+
+MULTI_K = (2, 4, 8)
+
+
+def alloc_scalars_multi(device, k: int) -> torch.Tensor:
+    return torch.zeros(k, S_NSLOTS, dtype=torch.float64, device=device)
+
+
+def alloc_partials_multi(device, k: int) -> torch.Tensor:
+    return torch.zeros(k, MAXG, dtype=torch.float64, device=device)
+
+
+def _multi_k(what: str, *mvs, rows=None) -> int:
+    k = mvs[0].shape[1] if mvs[0].dim() == 2 else -1
+    if k not in MULTI_K:
+        raise ValueError(f"{what}: multivectors must have shape (n, K) with K "
+                         f"in {MULTI_K}, got {tuple(mvs[0].shape)}")
+    for v in mvs:
+        if v.dtype != torch.float64:
+            raise TypeError(f"{what}: multivectors must be float64, got {v.dtype}")
+        if v.dim() != 2 or v.shape[1] != k:
+            raise ValueError(f"{what}: multivector shapes disagree: "
+                             f"{[tuple(m.shape) for m in mvs]}")
+        if not v.is_contiguous():
+            raise ValueError(f"{what}: multivectors must be contiguous")
+        if rows is not None and v.shape[0] < rows:
+            raise ValueError(f"{what}: multivector has {v.shape[0]} rows, "
+                             f"needs at least {rows}")
+    return k
+
+
+def spmm_bsell_supported(dof: int, k: int) -> bool:
+    return dof in (2, 3, 4) and k in MULTI_K
+
+
+def spmm_sell(sellptr, cols, vals, nrows, X, Y, *, partials=None, scal=None,
+              dotslot: int = -1, dot_accum: bool = False, perm=None) -> None:
+    k = _multi_k("spmm_sell", X, Y, rows=nrows)
+    if vals.dtype != torch.float64:
+        raise TypeError(f"spmm_sell: operator values must be float64, got {vals.dtype}")
+    if sellptr.numel() - 1 <= 0:
+        return
+    fuse = scal is not None and dotslot >= 0
+    for c in range(k):
+        y = torch.empty(nrows, dtype=torch.float64, device=X.device)
+        spmv_sell(sellptr, cols, vals, nrows, X[:, c].contiguous(), y,
+                  scal=scal.view(-1, S_NSLOTS)[c] if fuse else None,
+                  dotslot=dotslot, dot_accum=dot_accum, perm=perm)
+        Y[:nrows, c] = y
+
+
+def spmm_bsell(bptr, bcol, bvals, nnodes: int, dof: int, X, Y, *,
+               partials=None, scal=None, dotslot: int = -1,
+               dot_accum: bool = False) -> None:
+    n = nnodes * dof
+    k = _multi_k("spmm_bsell", X, Y, rows=n)
+    if bvals.dtype != torch.float64:
+        raise TypeError(f"spmm_bsell: operator values must be float64, got {bvals.dtype}")
+    if not spmm_bsell_supported(dof, k):
+        raise ValueError(f"spmm_bsell: no kernel for dof={dof}, K={k}")
+    if bptr.numel() - 1 <= 0:
+        return
+    fuse = scal is not None and dotslot >= 0
+    for c in range(k):
+        y = torch.empty(n, dtype=torch.float64, device=X.device)
+        spmv_bsell(bptr, bcol, bvals, nnodes, dof, X[:, c].contiguous(), y,
+                   scal=scal.view(-1, S_NSLOTS)[c] if fuse else None,
+                   dotslot=dotslot, dot_accum=dot_accum)
+        Y[:n, c] = y
+
+
+def dot_multi(X, Y, partials, scal, slot, n=None, accumulate=False) -> None:
+    n = X.shape[0] if n is None else n
+    k = _multi_k("dot_multi", X, Y, rows=n)
+    sc = scal.view(-1, S_NSLOTS)
+    for c in range(k):
+        d = torch.dot(X[:n, c], Y[:n, c])
+        sc[c, slot] = sc[c, slot] + d if accumulate else d
+
+
+def reduce_partials_multi(partials, nblocks: int, scal, slot,
+                          accumulate=False) -> None:
+    sc = scal.view(-1, S_NSLOTS)
+    pp = partials.view(-1, MAXG)
+    for c in range(sc.shape[0]):
+        d = pp[c, :nblocks].sum()
+        sc[c, slot] = sc[c, slot] + d if accumulate else d
+
+
+def cg_fused_update_multi(R, X, P, T, scal, partials, n) -> int:
+    """Matches k_cg_fused_update_multi: the new (r, r) of column c is left
+    in partials[c, 0] (always one block here); returns 1."""
+    k = _multi_k("cg_fused_update_multi", R, X, P, T, rows=n)
+    sc = scal.view(-1, S_NSLOTS)
+    pp = partials.view(-1, MAXG)
+    for c in range(k):
+        alpha = _sdiv(float(sc[c, S_RR]), float(sc[c, S_PT]))
+        R[:n, c] -= alpha * T[:n, c]
+        X[:n, c] += alpha * P[:n, c]
+        pp[c, 0] = torch.dot(R[:n, c], R[:n, c])
+    return 1
+
+
+def cg_finalize_multi(partials, nblocks: int, scal, rr_out) -> None:
+    sc = scal.view(-1, S_NSLOTS)
+    pp = partials.view(-1, MAXG)
+    for c in range(sc.shape[0]):
+        v = pp[c, :nblocks].sum()
+        sc[c, S_RR_PREV] = sc[c, S_RR].clone()
+        sc[c, S_RR] = v
+        rr_out[c] = v
+
+
+def daypx_ratio_multi(P, R, scal, num: int = S_RR, den: int = S_RR_PREV,
+                      n=None) -> None:
+    n = R.shape[0] if n is None else n
+    k = _multi_k("daypx_ratio_multi", P, R, rows=n)
+    sc = scal.view(-1, S_NSLOTS)
+    for c in range(k):
+        b = _sdiv(float(sc[c, num]), float(sc[c, den]))
+        P[:n, c] = b * P[:n, c] + R[:n, c]
+
+
 def pack_gather(sendbuf, x, idx) -> None:
     torch.index_select(x, 0, idx.long(), out=sendbuf)

@@ -124,6 +124,35 @@ def refine(res: SolveResult, tol: float, maxits: int, inner_rtol: float,
     return nres
 
 
+def check_multi_shapes(B, X, nowned: int, nlocal: int) -> int:
+    """Shape contract of ``solve_multi``: B (nowned, k), X (nlocal, k), fp64.
+    Returns k."""
+    import torch
+
+    if B.dim() != 2 or X.dim() != 2 or B.shape[1] < 1:
+        raise ValueError("solve_multi: B must have shape (nowned, k) and X "
+                         f"(nlocal, k); got {tuple(B.shape)} and {tuple(X.shape)}")
+    k = B.shape[1]
+    if B.shape[0] != nowned or tuple(X.shape) != (nlocal, k):
+        raise ValueError(f"solve_multi: expected B ({nowned}, k) and X "
+                         f"({nlocal}, k); got {tuple(B.shape)} and {tuple(X.shape)}")
+    if B.dtype != torch.float64 or X.dtype != torch.float64:
+        raise TypeError("solve_multi: B and X must be float64")
+    return k
+
+
+def solve_multi_by_column(solve, B, X, maxits, res_atol, res_rtol) -> list:
+    """Multiple right-hand sides as k independent ``solve`` calls on
+    contiguous copies of the columns; X is overwritten column by column."""
+    out = []
+    for c in range(B.shape[1]):
+        xc = X[:, c].contiguous()
+        out.append(solve(B[:, c].contiguous(), xc, maxits=maxits,
+                         res_atol=res_atol, res_rtol=res_rtol))
+        X[:, c] = xc
+    return out
+
+
 def cg_flops_per_iter(nnz_full: int, n: int) -> float:
     """Flops per classic-CG iteration: SpMV 2*nnz + 2 dots + 3 axpy-likes."""
     return 2.0 * nnz_full + 10.0 * n

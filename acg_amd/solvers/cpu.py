@@ -23,7 +23,8 @@ import torch
 from ..dist.halo import HaloExchange
 from ..ops import torch_ref as ops
 from ..part.subdomain import LocalSystem
-from .base import SolveResult, cg_flops_per_iter, refine
+from .base import (SolveResult, cg_flops_per_iter, check_multi_shapes, refine,
+                   solve_multi_by_column)
 
 
 class CGSolverCPU:
@@ -138,6 +139,15 @@ class CGSolverCPU:
         res.halo_bytes_sent = self.halo.bytes_sent
         res.halo_msgs_sent = self.halo.nmsgs_sent
         return res
+
+    def solve_multi(self, B: torch.Tensor, X: torch.Tensor, maxits: int = 100,
+                    res_atol: float = 0.0, res_rtol: float = 1e-9) -> list:
+        """k right-hand sides: ``B`` (nowned, k), ``X`` (nlocal, k), both
+        fp64; X is overwritten.  The plain loop over :meth:`solve`, one
+        SolveResult per column (the oracle of CGSolverHIP.solve_multi)."""
+        check_multi_shapes(B, X, self.n, self.nlocal)
+        return solve_multi_by_column(self.solve, B, X, maxits, res_atol,
+                                     res_rtol)
 
     # -- mixed precision: fp32-stored operator + fp64 refinement (beyond
     # reference; the oracle of CGSolverHIP.solve_mixed) -------------------

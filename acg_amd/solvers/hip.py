@@ -33,7 +33,8 @@ import torch
 from ..dist.halo import HaloExchange
 from ..ops import gpu_ops as ops
 from ..part.subdomain import LocalSystem
-from .base import SolveResult, cg_flops_per_iter, refine
+from .base import (SolveResult, cg_flops_per_iter, check_multi_shapes, refine,
+                   solve_multi_by_column)
 
 
 class CGSolverHIP:
@@ -137,6 +138,11 @@ class CGSolverHIP:
         self._graphs: dict = {}
         self._nstag = 0
         self._vals32 = None  # fp32 matA values, built by _lowprec_values
+        # solve_multi: columns per SpMM group, 2, 4 or 8.  A group of 8
+        # reads the matrix least often; on the 4.1 M-row Queen-shaped
+        # system two groups of 4 were nevertheless measured faster than
+        # one of 8 (profiles/multi_rhs.md, NOTES.md).
+        self.multi_group = 8
 
     def _pick_format(self, L, up, use_sell: bool, force: str | None) -> None:
         """Choose the matA operator format (reference analog: the choice
@@ -669,6 +675,180 @@ class CGSolverHIP:
                               idx_bytes_per_nnz=idxb)
             self.prof.reset()
         return res
+
+    # -- multiple right-hand sides (beyond reference) ----------------------
+
+    def _multi_fast_path(self) -> bool:
+        """The SpMM iteration exists for one rank with a SELL, sigma-SELL
+        or BSELL matA and no matO; everything else loops over solve()."""
+        serial = self.comm is None or self.comm.size == 1
+        return (serial and self.matfree is None and self.local.nnzO == 0
+                and self.n > 0
+                and (self.bsell is not None or self.sell is not None))
+
+    def _multi_kmax(self) -> int:
+        """Largest kernel-level K the operator format offers (a BSELL
+        (dof, K) pair may be refused by the op layer)."""
+        if self.multi_group not in ops.MULTI_K:
+            raise ValueError(f"multi_group must be one of {ops.MULTI_K}, "
+                             f"got {self.multi_group}")
+        ok = [k for k in ops.MULTI_K if k <= self.multi_group
+              and (self.bsell is None
+                   or ops.spmm_bsell_supported(self.bsell[3], k))]
+        return max(ok) if ok else 0
+
+    def solve_multi(self, B: torch.Tensor, X: torch.Tensor, maxits: int = 100,
+                    res_atol: float = 0.0, res_rtol: float = 1e-9) -> list:
+        """Classic CG for k right-hand sides of one matrix: ``B`` is
+        (nowned, k), ``X`` (nlocal, k), both fp64; X is overwritten and a
+        list of k SolveResult returned.
+
+        Fast path (one rank, SELL / sigma-SELL / BSELL matA, no matO): the
+        columns are processed in groups of up to 8 (``self.multi_group``),
+        a remainder padded with zero columns to the next size in
+        {2, 4, 8}; every iteration applies the operator to the whole group
+        with one SpMM, so each matrix entry and column index is read once
+        per group instead of once per column.
+        Each column has its own tolerance max(res_atol, res_rtol*||b_c||);
+        a group iterates until all its real columns have met theirs (a
+        column that converged early keeps iterating, which only improves
+        it).  A column's ``niterations`` is the first iteration at which it
+        met its tolerance; a column with b_c = 0 and x0_c = 0 is converged
+        at iteration 0 and stays exactly zero.  ``tsolve`` of every column
+        is its group's wall time.
+
+        Every other configuration (several ranks, CSR / hybrid formats, a
+        matO part, matrix-free) loops over :meth:`solve` column by column.
+        """
+        k = check_multi_shapes(B, X, self.n, self.nlocal)
+        kmax = self._multi_kmax() if self._multi_fast_path() else 0
+        if k == 1 or kmax == 0:
+            return solve_multi_by_column(self.solve, B, X, maxits, res_atol,
+                                         res_rtol)
+        out = []
+        for g0 in range(0, k, kmax):
+            kg = min(kmax, k - g0)
+            K = next(kk for kk in ops.MULTI_K if kk >= kg)
+            out += self._solve_multi_group(B[:, g0:g0 + kg], X[:, g0:g0 + kg],
+                                           K, maxits, res_atol, res_rtol)
+        return out
+
+    def _spmm(self, Xm: torch.Tensor, Y: torch.Tensor, scal, partials,
+              dotslot: int = -1) -> None:
+        fuse = dict(partials=partials, scal=scal, dotslot=dotslot) \
+            if dotslot >= 0 else {}
+        if self.bsell is not None:
+            bptr, bcol, bvals, dof = self.bsell
+            ops.spmm_bsell(bptr, bcol, bvals, self.n // dof, dof, Xm, Y, **fuse)
+        else:
+            sellptr, scols, svals = self.sell
+            ops.spmm_sell(sellptr, scols, svals, self.n, Xm, Y,
+                          perm=self.sell_perm, **fuse)
+
+    def _solve_multi_group(self, B, X, K: int, maxits: int, res_atol: float,
+                           res_rtol: float) -> list:
+        """One group of kg <= K columns on the SpMM iteration (eager, same
+        lag-2 host test as _solve_classic, reading the contiguous rr_out)."""
+        S = ops
+        n, kg = self.n, B.shape[1]
+        key = f"multi{K}"
+        ws = self._ws.get(key)
+        if ws is None:
+            def mv(rows):
+                return torch.zeros(rows, K, dtype=torch.float64,
+                                   device=self.device)
+            ws = self._ws[key] = {
+                "R": mv(n), "T": mv(n), "Bp": mv(n), "P": mv(self.nlocal),
+                "Xi": mv(self.nlocal),
+                "scal": S.alloc_scalars_multi(self.device, K),
+                "partials": S.alloc_partials_multi(self.device, K),
+                "rr_out": torch.zeros(K, dtype=torch.float64, device=self.device),
+            }
+        R, T, Bp, P, Xi = ws["R"], ws["T"], ws["Bp"], ws["P"], ws["Xi"]
+        scal, partials, rr_out = ws["scal"], ws["partials"], ws["rr_out"]
+        scal.zero_()
+        Bp.zero_()
+        Bp[:, :kg] = B
+        Xi.zero_()
+        Xi[:, :kg] = X
+        P.zero_()
+        torch.cuda.synchronize(self.device)
+        t0 = time.perf_counter()
+        S.dot_multi(Bp, Bp, partials, scal, S.S_BNRM2, n=n)
+        self._spmm(Xi, T, scal, partials)
+        torch.sub(Bp, T, out=R)
+        P[:n] = R
+        S.dot_multi(R, R, partials, scal, S.S_RR, n=n)
+        slab = scal.cpu()
+        bnrm = [math.sqrt(max(float(slab[c, S.S_BNRM2]), 0.0)) for c in range(kg)]
+        rr0 = [float(slab[c, S.S_RR]) for c in range(kg)]
+        rtol2 = [max(res_atol, res_rtol * bn) ** 2 for bn in bnrm]
+
+        def met(c: int, rr: float) -> bool:
+            return rr <= rtol2[c] if rtol2[c] > 0 else rr == 0.0
+
+        conv_it: list = [0 if met(c, rr0[c]) else None for c in range(kg)]
+        LAG = 2
+        hostbuf = [torch.zeros(K, dtype=torch.float64, pin_memory=True)
+                   for _ in range(LAG + 1)]
+        evdone = [torch.cuda.Event() for _ in range(LAG + 1)]
+
+        def check(j: int) -> bool:
+            evdone[j % (LAG + 1)].synchronize()
+            rrs = hostbuf[j % (LAG + 1)]
+            for c in range(kg):
+                rr = float(rrs[c])
+                if not math.isfinite(rr):
+                    raise FloatingPointError(
+                        f"CG diverged: rr={rr} in column {c} at it {j + 1}")
+                if conv_it[c] is None and met(c, rr):
+                    conv_it[c] = j + 1
+            return all(ci is not None for ci in conv_it)
+
+        nit = 0
+        done = all(ci is not None for ci in conv_it)
+        cur = torch.cuda.current_stream(self.device)
+        while not done and nit < maxits:
+            if nit >= LAG and check(nit - LAG):
+                done = True
+                break
+            with self.prof.span("spmvA"):
+                self._spmm(P, T, scal, partials, dotslot=S.S_PT)
+            with self.prof.span("update_classic"):
+                nb = S.cg_fused_update_multi(R, Xi, P, T, scal, partials, n)
+                S.cg_finalize_multi(partials, nb, scal, rr_out)
+            with self.prof.span("daypx"):
+                S.daypx_ratio_multi(P, R, scal, n=n)
+            j = nit % (LAG + 1)
+            hostbuf[j].copy_(rr_out, non_blocking=True)
+            evdone[j].record(cur)
+            nit += 1
+        if not done:
+            for j in range(max(nit - LAG, 0), nit):
+                if check(j):
+                    break
+        torch.cuda.synchronize(self.device)
+        tsolve = time.perf_counter() - t0
+        X.copy_(Xi[:, :kg])
+        slab = scal.cpu()
+        if self.prof.enabled:
+            self.prof.reset()
+        nnz_full = self.local.nnzA + self.local.nnzO
+        out = []
+        for c in range(kg):
+            rr = float(slab[c, S.S_RR])
+            res = SolveResult(solver="cg-hip-multi", maxits=maxits,
+                              res_atol=res_atol, res_rtol=res_rtol, nranks=1)
+            res.bnrm2 = bnrm[c]
+            res.r0nrm2 = math.sqrt(max(rr0[c], 0.0))
+            res.rnrm2 = math.sqrt(max(rr, 0.0))
+            res.converged = conv_it[c] is not None or met(c, rr)
+            res.niterations = conv_it[c] if conv_it[c] is not None else nit
+            res.tsolve = tsolve
+            res.nflops = res.niterations * cg_flops_per_iter(nnz_full, n)
+            out.append(res)
+        self.niterations_total += nit
+        return out
 
     # -- mixed precision: fp32-stored operator + fp64 refinement (beyond
     # reference; opt-in, no auto-selection) -------------------------------

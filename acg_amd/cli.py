@@ -8,7 +8,8 @@ write solution to stdout.  Multi-rank runs come from torchrun (one process
 per GPU, RCCL) instead of mpirun; --comm gloo supports CPU multi-process.
 
 Solvers: acg (GPU classic CG), acg-pipelined (GPU pipelined), acg-mixed /
-cpu-mixed (fp32-stored operator + fp64 refinement), cpu / cpu-pipelined
+cpu-mixed (fp32-stored operator + fp64 refinement), acg-block / cpu-block
+(block CG for several right-hand sides), cpu / cpu-pipelined
 (host torch), scipy / scipy-pipelined (independent
 oracle, the role PETSc KSPCG plays in the reference -- PETSc is not in
 this image).
@@ -49,8 +50,9 @@ def make_parser() -> argparse.ArgumentParser:
     p.add_argument("--seed", type=int, default=0, help="partitioner seed")
     p.add_argument("--solver", default=None,
                    choices=("acg", "acg-pipelined", "acg-device",
-                            "acg-jacobi", "acg-mixed", "cpu", "cpu-pipelined",
-                            "cpu-jacobi", "cpu-mixed", "scipy",
+                            "acg-jacobi", "acg-mixed", "acg-block", "cpu",
+                            "cpu-pipelined", "cpu-jacobi", "cpu-mixed",
+                            "cpu-block", "scipy",
                             "scipy-pipelined",
                             "petsc", "petsc-pipelined"),
                    help="default: acg on GPU, cpu otherwise.  petsc[-pipelined] "
@@ -84,7 +86,8 @@ def make_parser() -> argparse.ArgumentParser:
                         "(no b file): column 0 is the single-RHS vector, "
                         "column c > 0 is drawn from default_rng(seed + c).  "
                         "Multiple right-hand sides (also an n x K array b "
-                        "file) need --solver acg or cpu (beyond reference)")
+                        "file) need --solver acg, cpu, acg-block or cpu-block "
+                        "(beyond reference)")
     p.add_argument("--numfmt", default=None, help="printf format for output values")
     p.add_argument("--output-comm-matrix", action="store_true",
                    help="print the rank x rank halo send-count matrix to "
@@ -131,8 +134,10 @@ def _vector_from_mtx(m, n: int, what: str) -> np.ndarray:
     raise AcgError(ErrCode.INVALID_FORMAT, f"{what}: unsupported format {m.format!r}")
 
 
-# solvers that accept several right-hand sides (solve_multi)
-MULTI_RHS_SOLVERS = ("acg", "cpu")
+# solvers that accept several right-hand sides (solve_multi; the -block
+# solvers run block CG, solve_block, and are acg / cpu for one)
+MULTI_RHS_SOLVERS = ("acg", "cpu", "acg-block", "cpu-block")
+BLOCK_SOLVERS = ("acg-block", "cpu-block")
 
 
 def _rhs_from_mtx(m, n: int, what: str) -> np.ndarray:
@@ -152,7 +157,7 @@ def _check_multi_rhs(k: int, solver_name: str, args) -> None:
     if k > 1 and solver_name not in MULTI_RHS_SOLVERS:
         raise AcgError(ErrCode.NOT_SUPPORTED,
                        f"{k} right-hand sides are not supported by "
-                       f"{solver_name} (use acg or cpu)")
+                       f"{solver_name} (use acg, cpu, acg-block or cpu-block)")
     if k > 1 and (args.diff_atol > 0 or args.diff_rtol > 0):
         raise AcgError(ErrCode.NOT_SUPPORTED,
                        "--diff-atol/--diff-rtol are not supported with "
@@ -175,6 +180,7 @@ def main(argv=None) -> int:
                    "petsc-pipelined": "scipy-pipelined"}.get(solver_name,
                                                              solver_name)
     gpu_solver = solver_name.startswith("acg")
+    block_solver = solver_name in BLOCK_SOLVERS
     if args.nrhs < 1:
         raise AcgError(ErrCode.INVALID_VALUE, "--nrhs must be at least 1")
     _check_multi_rhs(args.nrhs, solver_name, args)
@@ -384,7 +390,7 @@ def main(argv=None) -> int:
             diff_requested = args.diff_atol > 0 or args.diff_rtol > 0
             mixed_kw = ({} if args.inner_rtol is None
                         else {"inner_rtol": args.inner_rtol})
-            if diff_requested and solver_name != "acg":
+            if diff_requested and solver_name not in ("acg", "acg-block"):
                 # reference parity: the GPU pipelined/device solvers REJECT
                 # diff tolerances (cghip.c:427, 1212) rather than silently
                 # iterating to maxits; classic implements them (see
@@ -393,12 +399,12 @@ def main(argv=None) -> int:
                                f"--diff-atol/--diff-rtol are not supported "
                                f"by {solver_name} (use acg or cpu)")
             if nrhs > 1:
+                solve_k = solver.solve_block if block_solver else solver.solve_multi
                 if args.warmup:
-                    solver.solve_multi(b, x.clone(), maxits=args.warmup,
-                                       res_rtol=0.0)
-                res = solver.solve_multi(b, x, maxits=args.max_iterations,
-                                         res_atol=args.residual_atol,
-                                         res_rtol=args.residual_rtol)
+                    solve_k(b, x.clone(), maxits=args.warmup, res_rtol=0.0)
+                res = solve_k(b, x, maxits=args.max_iterations,
+                              res_atol=args.residual_atol,
+                              res_rtol=args.residual_rtol)
             elif args.warmup:
                 if solver_name == "acg-pipelined":
                     solver.solve_pipelined(b, x.clone(), maxits=args.warmup,
@@ -446,9 +452,10 @@ def main(argv=None) -> int:
 
             solver = CGSolverCPU(S, comm=comm)
             if nrhs > 1:
-                res = solver.solve_multi(b, x, maxits=args.max_iterations,
-                                         res_atol=args.residual_atol,
-                                         res_rtol=args.residual_rtol)
+                solve_k = solver.solve_block if block_solver else solver.solve_multi
+                res = solve_k(b, x, maxits=args.max_iterations,
+                              res_atol=args.residual_atol,
+                              res_rtol=args.residual_rtol)
             elif solver_name == "cpu-pipelined":
                 res = solver.solve_pipelined(b, x, maxits=args.max_iterations,
                                              res_atol=args.residual_atol,
@@ -485,6 +492,10 @@ def main(argv=None) -> int:
         if nrhs > 1 and rank == 0:
             print(f"right-hand side {c} of {nrhs}:", file=sys.stderr)
         write_stats(rc, S, comm, file=sys.stderr)
+        if (args.verbose and rank == 0 and rc is not None
+                and rc.block_breakdown >= 0):
+            print(f"block CG handed over to the per-column iteration at "
+                  f"block iteration {rc.block_breakdown}", file=sys.stderr)
 
     # true-residual integrity check: ||b - A x|| of the returned iterate,
     # independent of the solver's residual recursion (bench.py computes the

@@ -606,6 +606,107 @@ def daypx_ratio_multi(P: torch.Tensor, R: torch.Tensor, scal: torch.Tensor,
                         num, den, _stream())
 
 
+# ---------------------------------------------------------------------------
+# Block CG (Dubrulle, orthonormalised residuals).  The block state is one
+# fp64 tensor of BS_SIZE slots (layout in kernels.hip next to the S_*
+# slots); the Gram partials live in an alloc_partials_multi(device, K)
+# tensor, pair p = (a <= b) of block g at p*BLOCK_MAXG + g.
+
+BS_LD = K.BS_LD
+BS_M = K.BS_M
+BS_XI = K.BS_XI
+BS_XIC = K.BS_XIC
+BS_G = K.BS_G
+BS_ZETA = K.BS_ZETA
+BS_ZINV = K.BS_ZINV
+BS_C = K.BS_C
+BS_FLAG = K.BS_FLAG
+BS_ITER = K.BS_ITER
+BS_SIZE = K.BS_SIZE
+BLOCK_MAXG = K.BLOCK_MAXG
+BLOCK_TAU = K.BLOCK_TAU
+
+
+def alloc_block_state(device) -> torch.Tensor:
+    return torch.zeros(BS_SIZE, dtype=torch.float64, device=device)
+
+
+def _block_bufs(what: str, k: int, kg: int | None, state: torch.Tensor | None,
+                partials: torch.Tensor | None, nblocks: int | None = None,
+                rr_out: torch.Tensor | None = None) -> None:
+    if k not in MULTI_K:
+        raise ValueError(f"{what}: K must be in {MULTI_K}, got {k}")
+    if kg is not None and not 1 <= kg <= k:
+        raise ValueError(f"{what}: kg must be in 1..{k}, got {kg}")
+    npairs = k * (k + 1) // 2
+    for t, need, nm in ((state, BS_SIZE, "state"),
+                        (partials, npairs * BLOCK_MAXG, "partials"),
+                        (rr_out, k + 2, "rr_out")):
+        if t is None:
+            continue
+        if (t.dtype != torch.float64 or not t.is_contiguous()
+                or t.numel() < need or not t.is_cuda):
+            raise ValueError(f"{what}: {nm} must be a contiguous float64 "
+                             f"device tensor of at least {need} elements")
+    if nblocks is not None and not 1 <= nblocks <= BLOCK_MAXG:
+        raise ValueError(f"{what}: nblocks must be in 1..{BLOCK_MAXG}, "
+                         f"got {nblocks}")
+
+
+def gram_multi(X: torch.Tensor, Y: torch.Tensor, partials: torch.Tensor,
+               n: int | None = None) -> int:
+    """Block partials of the upper triangle (a <= b) of X[:n]^T Y[:n] into
+    ``partials[p*BLOCK_MAXG + g]``; returns the number of blocks."""
+    n = X.shape[0] if n is None else n
+    k = _multi_k("gram_multi", X, Y, rows=n)
+    _block_bufs("gram_multi", k, None, None, partials)
+    return int(K.gram_multi(X.data_ptr(), Y.data_ptr(), n, k,
+                            partials.data_ptr(), _stream()))
+
+
+def block_update(X: torch.Tensor, S: torch.Tensor, Q: torch.Tensor,
+                 T: torch.Tensor, state: torch.Tensor, partials: torch.Tensor,
+                 n: int) -> int:
+    """X += S (xi C); Q <- W = Q - T xi on the first n rows; block partials
+    of the upper triangle of W^T W; returns the number of blocks.  Does
+    nothing when the breakdown flag of ``state`` is set."""
+    k = _multi_k("block_update", X, S, Q, T, rows=n)
+    _block_bufs("block_update", k, None, state, partials)
+    return int(K.block_update(X.data_ptr(), S.data_ptr(), Q.data_ptr(),
+                              T.data_ptr(), n, k, state.data_ptr(),
+                              partials.data_ptr(), _stream()))
+
+
+def block_ortho(Q: torch.Tensor, S: torch.Tensor, state: torch.Tensor,
+                n: int) -> None:
+    """Q <- Q zeta^-1; S <- Q + S zeta^T on the first n rows (ghost rows of
+    S are not written).  Does nothing when the breakdown flag is set."""
+    k = _multi_k("block_ortho", Q, S, rows=n)
+    _block_bufs("block_ortho", k, None, state, None)
+    K.block_ortho(Q.data_ptr(), S.data_ptr(), n, k, state.data_ptr(), _stream())
+
+
+def block_coef_alpha(partials: torch.Tensor, nblocks: int, state: torch.Tensor,
+                     k: int, kg: int, it: int) -> None:
+    """M = sum of the Gram partials (mirrored, identity beyond kg),
+    pivot-tested Cholesky, xi = M^-1, xi C.  A failed pivot sets the sticky
+    flag and records ``it``."""
+    _block_bufs("block_coef_alpha", k, kg, state, partials, nblocks)
+    K.block_coef_alpha(partials.data_ptr(), nblocks, state.data_ptr(), k, kg,
+                       it, _stream())
+
+
+def block_coef_beta(partials: torch.Tensor, nblocks: int, state: torch.Tensor,
+                    rr_out: torch.Tensor, k: int, kg: int, it: int,
+                    init: bool = False) -> None:
+    """G = sum of the Gram partials, zeta = chol(G)^T, zeta^-1, C <- zeta C
+    (``init``: C = zeta); rr_out[c] = ||C[:, c]||^2 for c < kg, rr_out[k] the
+    breakdown flag and rr_out[k+1] the iteration it was set at (-1: never)."""
+    _block_bufs("block_coef_beta", k, kg, state, partials, nblocks, rr_out)
+    K.block_coef_beta(partials.data_ptr(), nblocks, state.data_ptr(),
+                      rr_out.data_ptr(), k, kg, it, bool(init), _stream())
+
+
 def pack_gather(sendbuf: torch.Tensor, x: torch.Tensor, idx: torch.Tensor) -> None:
     K.pack_gather(sendbuf.data_ptr(), x.data_ptr(), idx.data_ptr(),
                   1 if idx.dtype == torch.int64 else 0,

@@ -31,7 +31,10 @@
 //   7. multiple right-hand sides: SELL / BSELL SpMM over K = 2, 4, 8
 //      interleaved vectors (each matrix value and index read once for K
 //      products) and the per-column dot / fused update / finalize / daypx
-//      kernels of the batched classic CG.
+//      kernels of the batched classic CG,
+//   8. block CG over the same multivectors: K x K Gram reductions, the
+//      fused block update, the Cholesky-QR re-orthonormalisation and the
+//      two one-workgroup dense coefficient kernels.
 //
 // The scalar slab layout (fp64 slots) is shared with solvers/hip.py:
 #define S_RR 0         // (r,r) current
@@ -43,6 +46,27 @@
 #define S_GAMMA_PREV 6
 #define S_ALPHA_PREV 7
 #define S_NSLOTS 8
+
+// Block-CG state (section 8): one contiguous fp64 tensor of BS_SIZE slots,
+// shared with solvers/hip.py and mirrored in ops/torch_ref.py.  Every
+// small matrix owns an 8 x 8 row-major region (entry (a, b) at
+// base + a*BS_LD + b) whatever the kernel width K is; a width-K kernel
+// reads and writes the leading K x K entries only.
+#define BS_LD 8
+#define BS_M 0         // M = S^T T (mirrored, rows/cols >= kg identity)
+#define BS_XI 64       // xi = M^-1
+#define BS_XIC 128     // xi C
+#define BS_G 192       // G = W^T W (mirrored, rows/cols >= kg identity)
+#define BS_ZETA 256    // zeta, upper triangular, G = zeta^T zeta
+#define BS_ZINV 320    // zeta^-1, upper triangular
+#define BS_C 384       // C: the residual is R = Q C
+#define BS_FLAG 448    // sticky breakdown flag: 0 or 1
+#define BS_ITER 449    // block iteration at which the flag was set
+#define BS_SIZE 456
+// block-CG Gram partials: pair p = (a <= b) of block g at p*BLOCK_MAXG + g
+#define BLOCK_MAXG 2048
+// Cholesky pivot test: breakdown if d_j <= BLOCK_TAU * (diagonal entry)
+#define BLOCK_TAU 1e-6
 
 // partials scratch: [0, MAXG) first accumulator, [MAXG, 2*MAXG) second
 #define MAXG 16384
@@ -2026,6 +2050,382 @@ k_daypx_ratio_multi(double* __restrict__ P, const double* __restrict__ R,
 }
 
 // ---------------------------------------------------------------------------
+// Block CG (Dubrulle's form with orthonormalised residuals, the QR step as
+// Cholesky-QR) for one group of kg <= K columns, K in {2, 4, 8}:
+//
+//   T = A S (k_spmm_*);  M = S^T T (k_gram_multi);  xi = M^-1, xi C
+//   (k_block_coef_alpha);  X += S (xi C), W = Q - T xi, partials of W^T W
+//   (k_block_update);  zeta = chol(W^T W)^T, zeta^-1, C <- zeta C, the
+//   residual norms (k_block_coef_beta);  Q <- W zeta^-1, S <- Q + S zeta^T
+//   (k_block_ortho).
+//
+// The n-sized kernels map ONE ROW PER THREAD per grid-stride trip: the
+// K x K coupling needs the whole row in registers, and a Gram entry is a
+// sum over rows.  Grams are reduced like every dot here: K(K+1)/2 block
+// partials, summed in a fixed order by the one-block coefficient kernels
+// (no floating-point atomics).  The state layout is at the top of the
+// file.  Once BS_FLAG is set every kernel of the iteration returns before
+// its first store, so X, Q, S, C and rr_out[0..K) keep their values.
+
+static inline long block_grid(long n) {
+    long blocks = (n + BLOCK - 1) / BLOCK;
+    if (blocks > BLOCK_MAXG) blocks = BLOCK_MAXG;
+    if (blocks < 1) blocks = 1;
+    return blocks;
+}
+
+template <int K>
+__device__ __forceinline__ void ld_row_nt(const double* __restrict__ p, double (&v)[K]) {
+    const d2_t* __restrict__ q = (const d2_t*)p;
+    #pragma unroll
+    for (int h = 0; h < K / 2; ++h) {
+        const d2_t w = ld_nt(q + h);
+        v[2 * h] = w.x;
+        v[2 * h + 1] = w.y;
+    }
+}
+
+template <int K>
+__device__ __forceinline__ void st_row_nt(double* __restrict__ p, const double (&v)[K]) {
+    d2_t* __restrict__ q = (d2_t*)p;
+    #pragma unroll
+    for (int h = 0; h < K / 2; ++h) {
+        d2_t w;
+        w.x = v[2 * h];
+        w.y = v[2 * h + 1];
+        __builtin_nontemporal_store(w, q + h);
+    }
+}
+
+// acc += upper triangle of x y^T; pair (a, b), a <= b, in row-major order
+template <int K>
+__device__ __forceinline__ void gram_accum(const double (&x)[K], const double (&y)[K],
+                                           double (&acc)[K * (K + 1) / 2]) {
+    #pragma unroll
+    for (int a = 0; a < K; ++a) {
+        #pragma unroll
+        for (int b = a; b < K; ++b)
+            acc[a * K - (a * (a - 1)) / 2 + (b - a)] += x[a] * y[b];
+    }
+}
+
+// K(K+1)/2 block sums -> partials[p*BLOCK_MAXG + blockIdx.x]
+template <int K>
+__device__ __forceinline__ void gram_block_reduce(const double (&acc)[K * (K + 1) / 2],
+                                                  double* __restrict__ partials) {
+    constexpr int NP = K * (K + 1) / 2;
+    __shared__ double w[BLOCK / WAVE][NP];
+    const int lane = threadIdx.x & (WAVE - 1);
+    const int wid = threadIdx.x >> 6;
+    #pragma unroll
+    for (int p = 0; p < NP; ++p) {
+        double v = acc[p];
+        #pragma unroll
+        for (int off = WAVE / 2; off > 0; off >>= 1)
+            v += __shfl_down(v, off, WAVE);
+        if (lane == 0) w[wid][p] = v;
+    }
+    __syncthreads();
+    if (threadIdx.x < NP) {
+        double v = 0.0;
+        #pragma unroll
+        for (int q = 0; q < BLOCK / WAVE; ++q) v += w[q][threadIdx.x];
+        partials[(long)threadIdx.x * BLOCK_MAXG + blockIdx.x] = v;
+    }
+}
+
+// upper triangle of X^T Y over the first n rows
+template <int K>
+__global__ void __launch_bounds__(BLOCK)
+k_gram_multi(const double* __restrict__ X, const double* __restrict__ Y,
+             long n, double* __restrict__ partials) {
+    double acc[K * (K + 1) / 2];
+    #pragma unroll
+    for (int p = 0; p < K * (K + 1) / 2; ++p) acc[p] = 0.0;
+    const long stride = (long)gridDim.x * BLOCK;
+    for (long i = (long)blockIdx.x * BLOCK + threadIdx.x; i < n; i += stride) {
+        double x[K], y[K];
+        ld_row<K>(X + i * K, x);
+        ld_row<K>(Y + i * K, y);
+        gram_accum<K>(x, y, acc);
+    }
+    gram_block_reduce<K>(acc, partials);
+}
+
+// X += S (xi C);  W = Q - T xi over Q;  block partials of W^T W.  The
+// 2 K^2 coefficients are staged in LDS once per block (broadcast reads).
+// X and T are single-use streams (NT), S and Q are read again by
+// k_block_ortho.
+template <int K>
+__global__ void __launch_bounds__(BLOCK)
+k_block_update(double* __restrict__ X, const double* __restrict__ S,
+               double* __restrict__ Q, const double* __restrict__ T, long n,
+               const double* __restrict__ state, double* __restrict__ partials) {
+    if (state[BS_FLAG] != 0.0) return;
+    __shared__ double cxi[K * K], cxc[K * K];
+    if (threadIdx.x < K * K) {
+        const int a = threadIdx.x / K, c = threadIdx.x % K;
+        cxi[threadIdx.x] = state[BS_XI + a * BS_LD + c];
+        cxc[threadIdx.x] = state[BS_XIC + a * BS_LD + c];
+    }
+    __syncthreads();
+    double acc[K * (K + 1) / 2];
+    #pragma unroll
+    for (int p = 0; p < K * (K + 1) / 2; ++p) acc[p] = 0.0;
+    const long stride = (long)gridDim.x * BLOCK;
+    for (long i = (long)blockIdx.x * BLOCK + threadIdx.x; i < n; i += stride) {
+        // keep the LDS coefficient reads inside the trip: hoisted out of
+        // the loop, the 2 K^2 values alone fill the register file at K = 8
+        asm volatile("" ::: "memory");
+        double s[K], x[K], t[K], w[K];
+        ld_row<K>(S + i * K, s);
+        ld_row_nt<K>(X + i * K, x);
+        ld_row_nt<K>(T + i * K, t);
+        ld_row<K>(Q + i * K, w);
+        #pragma unroll
+        for (int a = 0; a < K; ++a) {
+            #pragma unroll
+            for (int c = 0; c < K; ++c) x[c] += s[a] * cxc[a * K + c];
+        }
+        st_row_nt<K>(X + i * K, x);
+        #pragma unroll
+        for (int a = 0; a < K; ++a) {
+            #pragma unroll
+            for (int c = 0; c < K; ++c) w[c] -= t[a] * cxi[a * K + c];
+        }
+        st_row<K>(Q + i * K, w);
+        gram_accum<K>(w, w, acc);
+    }
+    gram_block_reduce<K>(acc, partials);
+}
+
+// Q <- W zeta^-1;  S <- Q + S zeta^T on the first n rows.  (NT accesses
+// for Q, meant to keep S cache-resident for the SpMM that follows, were
+// measured and bought nothing: profiles/block_cg.md.)
+template <int K>
+__global__ void __launch_bounds__(BLOCK)
+k_block_ortho(double* __restrict__ Q, double* __restrict__ S, long n,
+              const double* __restrict__ state) {
+    if (state[BS_FLAG] != 0.0) return;
+    __shared__ double czi[K * K], cz[K * K];
+    if (threadIdx.x < K * K) {
+        const int a = threadIdx.x / K, c = threadIdx.x % K;
+        czi[threadIdx.x] = state[BS_ZINV + a * BS_LD + c];
+        cz[threadIdx.x] = state[BS_ZETA + a * BS_LD + c];
+    }
+    __syncthreads();
+    const long stride = (long)gridDim.x * BLOCK;
+    for (long i = (long)blockIdx.x * BLOCK + threadIdx.x; i < n; i += stride) {
+        asm volatile("" ::: "memory");  // as in k_block_update
+        double w[K], s[K], q[K], sn[K];
+        ld_row<K>(Q + i * K, w);
+        ld_row<K>(S + i * K, s);
+        #pragma unroll
+        for (int c = 0; c < K; ++c) q[c] = 0.0;
+        #pragma unroll
+        for (int a = 0; a < K; ++a) {
+            #pragma unroll
+            for (int c = 0; c < K; ++c) q[c] += w[a] * czi[a * K + c];
+        }
+        #pragma unroll
+        for (int c = 0; c < K; ++c) sn[c] = q[c];
+        #pragma unroll
+        for (int a = 0; a < K; ++a) {
+            #pragma unroll
+            for (int c = 0; c < K; ++c) sn[c] += s[a] * cz[c * K + a];  // zeta^T
+        }
+        st_row<K>(Q + i * K, q);
+        st_row<K>(S + i * K, sn);
+    }
+}
+
+// One workgroup: sum the Gram partials of every pair into the upper
+// triangle of g.  64 / 16 / 4 threads per pair (K = 2 / 4 / 8: the largest
+// power of two with pairs * threads <= BLOCK), each summing a fixed strided
+// subsequence in four independent accumulators (the loads pipeline instead
+// of waiting on one add chain), joined by xor shuffles (a + b on both
+// sides, so every thread of a pair holds the same bits).
+__device__ __forceinline__ void block_sum_pairs(const double* __restrict__ partials,
+                                                int nblocks, int K,
+                                                double (*g)[BS_LD]) {
+    const int tpp = K == 2 ? 64 : (K == 4 ? 16 : 4);
+    const int p = threadIdx.x / tpp, sub = threadIdx.x % tpp;
+    const int np = K * (K + 1) / 2;
+    double a0 = 0.0, a1 = 0.0, a2 = 0.0, a3 = 0.0;
+    if (p < np) {
+        const double* __restrict__ q = partials + (long)p * BLOCK_MAXG;
+        int i = sub;
+        for (; i + 3 * tpp < nblocks; i += 4 * tpp) {
+            a0 += q[i];
+            a1 += q[i + tpp];
+            a2 += q[i + 2 * tpp];
+            a3 += q[i + 3 * tpp];
+        }
+        for (; i < nblocks; i += tpp) a0 += q[i];
+    }
+    double v = (a0 + a1) + (a2 + a3);
+    for (int off = 1; off < tpp; off <<= 1) v += __shfl_xor(v, off, WAVE);
+    if (sub == 0 && p < np) {
+        int a = 0, q = p;
+        while (q >= K - a) { q -= K - a; ++a; }
+        g[a][a + q] = v;
+    }
+}
+
+// Pivot-tested Cholesky g = l l^T of the leading kg x kg block (serial,
+// one thread; l starts as the identity).  Pivot d_j is tested against the
+// diagonal entry it came from: d_j / g_jj is the squared sine of the angle
+// between column j and the span of the columns before it.
+__device__ __forceinline__ bool block_chol(const double (*g)[BS_LD],
+                                           double (*l)[BS_LD], int kg) {
+    for (int j = 0; j < kg; ++j) {
+        double d = g[j][j];
+        for (int k = 0; k < j; ++k) d -= l[j][k] * l[j][k];
+        if (!__builtin_isfinite(d) || !(d > BLOCK_TAU * g[j][j])) return false;
+        const double ljj = sqrt(d);
+        l[j][j] = ljj;
+        for (int i = j + 1; i < kg; ++i) {
+            double s = g[i][j];
+            for (int k = 0; k < j; ++k) s -= l[i][k] * l[j][k];
+            l[i][j] = s / ljj;
+        }
+    }
+    return true;
+}
+
+// sums -> symmetric g with rows/cols >= kg the identity; l = identity.
+// Returns this thread's entry of g (threads < 64: a = t/8, b = t%8).
+__device__ __forceinline__ double block_gram_setup(const double* __restrict__ partials,
+                                                   int nblocks, int K, int kg,
+                                                   double (*g)[BS_LD],
+                                                   double (*l)[BS_LD]) {
+    const int a = threadIdx.x >> 3, b = threadIdx.x & 7;
+    block_sum_pairs(partials, nblocks, K, g);
+    if (threadIdx.x < 64) l[a][b] = (a == b) ? 1.0 : 0.0;
+    __syncthreads();
+    double m = 0.0;
+    if (threadIdx.x < 64)
+        m = (a < kg && b < kg) ? (a <= b ? g[a][b] : g[b][a]) : (a == b ? 1.0 : 0.0);
+    __syncthreads();
+    if (threadIdx.x < 64) g[a][b] = m;
+    __syncthreads();
+    return m;
+}
+
+// M from the partials, xi = M^-1 (column c: L y = e_c, L^T x = y, so the
+// backward error of a Cholesky solve holds per column), xi C
+__global__ void __launch_bounds__(BLOCK)
+k_block_coef_alpha(const double* __restrict__ partials, int nblocks,
+                   double* state, int K, int kg, int it) {
+    if (state[BS_FLAG] != 0.0) return;
+    __shared__ double g[BS_LD][BS_LD], l[BS_LD][BS_LD], xi[BS_LD][BS_LD];
+    __shared__ int ok;
+    const int t = threadIdx.x, a = t >> 3, b = t & 7;
+    const bool mine = t < 64 && a < K && b < K;
+    const double m = block_gram_setup(partials, nblocks, K, kg, g, l);
+    if (t < 64) xi[a][b] = (a == b) ? 1.0 : 0.0;
+    if (t == 0) ok = block_chol(g, l, kg) ? 1 : 0;
+    __syncthreads();
+    if (mine) state[BS_M + a * BS_LD + b] = m;
+    if (!ok) {
+        if (t == 0) {
+            state[BS_FLAG] = 1.0;
+            state[BS_ITER] = (double)it;
+        }
+        return;
+    }
+    if (t < kg) {
+        const int c = t;
+        for (int i = c; i < kg; ++i) {
+            double s = (i == c) ? 1.0 : 0.0;
+            for (int k = c; k < i; ++k) s -= l[i][k] * xi[k][c];
+            xi[i][c] = s / l[i][i];
+        }
+        for (int i = kg - 1; i >= 0; --i) {
+            double s = xi[i][c];
+            for (int k = i + 1; k < kg; ++k) s -= l[k][i] * xi[k][c];
+            xi[i][c] = s / l[i][i];
+        }
+    }
+    __syncthreads();
+    if (mine) {
+        double s = 0.0;
+        for (int k = 0; k < K; ++k) s += xi[a][k] * state[BS_C + k * BS_LD + b];
+        state[BS_XI + a * BS_LD + b] = xi[a][b];
+        state[BS_XIC + a * BS_LD + b] = s;
+    }
+}
+
+// G from the partials, zeta = chol(G)^T, zeta^-1 (column c by back
+// substitution of zeta x = e_c), C <- zeta C (init: C = zeta),
+// rr_out[c] = ||C[:, c]||^2 for c < kg, rr_out[K] / rr_out[K+1] = flag /
+// iteration.  With the flag already set only the latter two are written,
+// so a breakdown found by k_block_coef_alpha reaches the host copy too.
+__global__ void __launch_bounds__(BLOCK)
+k_block_coef_beta(const double* __restrict__ partials, int nblocks,
+                  double* state, double* __restrict__ rr_out, int K, int kg,
+                  int it, int init) {
+    const int t = threadIdx.x, a = t >> 3, b = t & 7;
+    if (state[BS_FLAG] != 0.0) {
+        if (t == 0) {
+            rr_out[K] = state[BS_FLAG];
+            rr_out[K + 1] = state[BS_ITER];
+        }
+        return;
+    }
+    __shared__ double g[BS_LD][BS_LD], l[BS_LD][BS_LD], zi[BS_LD][BS_LD],
+                      cs[BS_LD][BS_LD];
+    __shared__ int ok;
+    const bool mine = t < 64 && a < K && b < K;
+    const double m = block_gram_setup(partials, nblocks, K, kg, g, l);
+    if (t < 64) zi[a][b] = (a == b) ? 1.0 : 0.0;
+    if (t == 0) ok = block_chol(g, l, kg) ? 1 : 0;
+    __syncthreads();
+    if (mine) state[BS_G + a * BS_LD + b] = m;
+    if (!ok) {
+        if (t == 0) {
+            state[BS_FLAG] = 1.0;
+            state[BS_ITER] = (double)it;
+            rr_out[K] = 1.0;
+            rr_out[K + 1] = (double)it;
+        }
+        return;
+    }
+    if (t < kg) {
+        const int c = t;
+        for (int i = c; i >= 0; --i) {
+            double s = (i == c) ? 1.0 : 0.0;
+            for (int k = i + 1; k <= c; ++k) s -= l[k][i] * zi[k][c];
+            zi[i][c] = s / l[i][i];
+        }
+    }
+    double cn = 0.0;
+    if (mine) {
+        if (init) {
+            cn = l[b][a];
+        } else {
+            for (int k = 0; k < K; ++k) cn += l[k][a] * state[BS_C + k * BS_LD + b];
+        }
+        cs[a][b] = cn;
+    }
+    __syncthreads();  // every read of the old C is done; zi and cs complete
+    if (mine) {
+        state[BS_ZETA + a * BS_LD + b] = l[b][a];
+        state[BS_ZINV + a * BS_LD + b] = zi[a][b];
+        state[BS_C + a * BS_LD + b] = cn;
+    }
+    if (t < kg) {
+        double s = 0.0;
+        for (int k = 0; k < K; ++k) s += cs[k][t] * cs[k][t];
+        rr_out[t] = s;
+    }
+    if (t == 0) {
+        rr_out[K] = 0.0;
+        rr_out[K + 1] = -1.0;
+    }
+}
+
+// ---------------------------------------------------------------------------
 // host-side launchers (pybind).  Tensors arrive as raw device pointers +
 // sizes + the caller's HIP stream handle (torch.cuda.current_stream().cuda_stream);
 // no torch C++ dependency, no hipify, plain HIP throughout.
@@ -2562,6 +2962,74 @@ void daypx_ratio_multi(uintptr_t P, uintptr_t R, long n, int k, uintptr_t scal,
     #undef DAYPX_K
     check_hip("daypx_ratio_multi");
 }
+
+// -- block CG -------------------------------------------------------------------
+
+static void block_check(const char* what, int k, int kg, int nblocks) {
+    if (k != 2 && k != 4 && k != 8)
+        throw std::invalid_argument(std::string(what) + ": K must be 2, 4 or 8");
+    if (kg < 1 || kg > k)
+        throw std::invalid_argument(std::string(what) + ": kg must be in 1..K");
+    if (nblocks < 1 || nblocks > BLOCK_MAXG)
+        throw std::invalid_argument(std::string(what) + ": nblocks out of range");
+}
+
+// returns the number of blocks (= partials per pair)
+long gram_multi(uintptr_t X, uintptr_t Y, long n, int k, uintptr_t partials,
+                uintptr_t stream) {
+    const long blocks = block_grid(n);
+    dim3 g((unsigned)blocks), b(BLOCK);
+    #define GRAM_K(KK) \
+        hipLaunchKernelGGL(k_gram_multi<KK>, g, b, 0, S(stream), (const double*)X, \
+                           (const double*)Y, n, (double*)partials)
+    DISPATCH_K(k, "gram_multi", GRAM_K)
+    #undef GRAM_K
+    check_hip("gram_multi");
+    return blocks;
+}
+
+long block_update(uintptr_t X, uintptr_t Sm, uintptr_t Q, uintptr_t T, long n, int k,
+                  uintptr_t state, uintptr_t partials, uintptr_t stream) {
+    const long blocks = block_grid(n);
+    dim3 g((unsigned)blocks), b(BLOCK);
+    #define BUPD_K(KK) \
+        hipLaunchKernelGGL(k_block_update<KK>, g, b, 0, S(stream), (double*)X, \
+                           (const double*)Sm, (double*)Q, (const double*)T, n, \
+                           (const double*)state, (double*)partials)
+    DISPATCH_K(k, "block_update", BUPD_K)
+    #undef BUPD_K
+    check_hip("block_update");
+    return blocks;
+}
+
+void block_ortho(uintptr_t Q, uintptr_t Sm, long n, int k, uintptr_t state,
+                 uintptr_t stream) {
+    dim3 g((unsigned)block_grid(n)), b(BLOCK);
+    #define BORTHO_K(KK) \
+        hipLaunchKernelGGL(k_block_ortho<KK>, g, b, 0, S(stream), (double*)Q, \
+                           (double*)Sm, n, (const double*)state)
+    DISPATCH_K(k, "block_ortho", BORTHO_K)
+    #undef BORTHO_K
+    check_hip("block_ortho");
+}
+
+void block_coef_alpha(uintptr_t partials, int nblocks, uintptr_t state, int k,
+                      int kg, int it, uintptr_t stream) {
+    block_check("block_coef_alpha", k, kg, nblocks);
+    hipLaunchKernelGGL(k_block_coef_alpha, dim3(1), dim3(BLOCK), 0, S(stream),
+                       (const double*)partials, nblocks, (double*)state, k, kg, it);
+    check_hip("block_coef_alpha");
+}
+
+void block_coef_beta(uintptr_t partials, int nblocks, uintptr_t state,
+                     uintptr_t rr_out, int k, int kg, int it, bool init,
+                     uintptr_t stream) {
+    block_check("block_coef_beta", k, kg, nblocks);
+    hipLaunchKernelGGL(k_block_coef_beta, dim3(1), dim3(BLOCK), 0, S(stream),
+                       (const double*)partials, nblocks, (double*)state,
+                       (double*)rr_out, k, kg, it, init ? 1 : 0);
+    check_hip("block_coef_beta");
+}
 #undef DISPATCH_K
 
 PYBIND11_MODULE(_acg_kernels, m) {
@@ -2574,6 +3042,24 @@ PYBIND11_MODULE(_acg_kernels, m) {
     m.def("cg_fused_update_multi", &cg_fused_update_multi);
     m.def("cg_finalize_multi", &cg_finalize_multi);
     m.def("daypx_ratio_multi", &daypx_ratio_multi);
+    m.def("gram_multi", &gram_multi);
+    m.def("block_update", &block_update);
+    m.def("block_ortho", &block_ortho);
+    m.def("block_coef_alpha", &block_coef_alpha);
+    m.def("block_coef_beta", &block_coef_beta);
+    m.attr("BS_LD") = BS_LD;
+    m.attr("BS_M") = BS_M;
+    m.attr("BS_XI") = BS_XI;
+    m.attr("BS_XIC") = BS_XIC;
+    m.attr("BS_G") = BS_G;
+    m.attr("BS_ZETA") = BS_ZETA;
+    m.attr("BS_ZINV") = BS_ZINV;
+    m.attr("BS_C") = BS_C;
+    m.attr("BS_FLAG") = BS_FLAG;
+    m.attr("BS_ITER") = BS_ITER;
+    m.attr("BS_SIZE") = BS_SIZE;
+    m.attr("BLOCK_MAXG") = BLOCK_MAXG;
+    m.attr("BLOCK_TAU") = BLOCK_TAU;
     m.def("spmv", &spmv);
     m.def("spmv_binned", &spmv_binned);
     m.def("spmv_sell", &spmv_sell);

@@ -9,6 +9,8 @@ arguments are accepted for API parity but unused (torch reduces directly).
 
 from __future__ import annotations
 
+import math
+
 import torch
 
 # keep slot numbering identical to kernels.hip
@@ -752,6 +754,171 @@ def daypx_ratio_multi(P, R, scal, num: int = S_RR, den: int = S_RR_PREV,
     for c in range(k):
         b = _sdiv(float(sc[c, num]), float(sc[c, den]))
         P[:n, c] = b * P[:n, c] + R[:n, c]
+
+
+# ---------------------------------------------------------------------------
+# Block CG (same state layout as kernels.hip: every small matrix owns an
+# 8 x 8 row-major region of the BS_SIZE-slot fp64 state tensor, a width-K
+# op touches the leading K x K entries; Gram partials of pair p = (a <= b),
+# row-major over the upper triangle, at partials[p*BLOCK_MAXG + block]).
+
+BS_LD = 8
+BS_M, BS_XI, BS_XIC, BS_G, BS_ZETA, BS_ZINV, BS_C = 0, 64, 128, 192, 256, 320, 384
+BS_FLAG, BS_ITER, BS_SIZE = 448, 449, 456
+BLOCK_MAXG = 2048
+BLOCK_TAU = 1e-6
+
+
+def alloc_block_state(device="cpu") -> torch.Tensor:
+    return torch.zeros(BS_SIZE, dtype=torch.float64, device=device)
+
+
+def _block_region(state, base: int, k: int):
+    """Writable (k, k) view of one matrix of the state."""
+    return state[base:base + BS_LD * BS_LD].view(BS_LD, BS_LD)[:k, :k]
+
+
+def _block_pairs(k: int):
+    return [(a, b) for a in range(k) for b in range(a, k)]
+
+
+def _block_write_partials(G, partials, k: int) -> int:
+    flat = partials.view(-1)
+    for p, (a, b) in enumerate(_block_pairs(k)):
+        flat[p * BLOCK_MAXG] = G[a, b]
+    return 1
+
+
+def _block_sym(partials, nblocks: int, k: int, kg: int):
+    """Symmetric (k, k) Gram from the partials of its upper triangle; rows
+    and columns >= kg are the identity."""
+    flat = partials.view(-1)
+    g = torch.eye(k, dtype=torch.float64)
+    for p, (a, b) in enumerate(_block_pairs(k)):
+        if b < kg:
+            v = float(flat[p * BLOCK_MAXG:p * BLOCK_MAXG + nblocks].sum())
+            g[a, b] = v
+            g[b, a] = v
+    return g
+
+
+def _block_chol(g, kg: int):
+    """Pivot-tested Cholesky g = l l^T of the leading kg x kg block, the
+    rest of l the identity; None on breakdown (pivot d_j not finite or
+    d_j <= BLOCK_TAU * g_jj)."""
+    k = g.shape[0]
+    l = [[1.0 if i == j else 0.0 for j in range(k)] for i in range(k)]
+    for j in range(kg):
+        d = float(g[j, j])
+        for q in range(j):
+            d -= l[j][q] * l[j][q]
+        if not math.isfinite(d) or not d > BLOCK_TAU * float(g[j, j]):
+            return None
+        ljj = math.sqrt(d)
+        l[j][j] = ljj
+        for i in range(j + 1, kg):
+            s = float(g[i, j])
+            for q in range(j):
+                s -= l[i][q] * l[j][q]
+            l[i][j] = s / ljj
+    return torch.tensor(l, dtype=torch.float64)
+
+
+def _block_newc(zeta, C):
+    return zeta @ C
+
+
+def _block_flagged(state) -> bool:
+    return float(state[BS_FLAG]) != 0.0
+
+
+def gram_multi(X, Y, partials, n=None) -> int:
+    """Upper triangle of X[:n]^T Y[:n] as ONE block of partials; returns 1."""
+    n = X.shape[0] if n is None else n
+    k = _multi_k("gram_multi", X, Y, rows=n)
+    return _block_write_partials(X[:n].T @ Y[:n], partials, k)
+
+
+def block_update(X, S, Q, T, state, partials, n) -> int:
+    k = _multi_k("block_update", X, S, Q, T, rows=n)
+    if _block_flagged(state):
+        return 1
+    xi = _block_region(state, BS_XI, k)
+    xic = _block_region(state, BS_XIC, k)
+    X[:n] += S[:n] @ xic
+    Q[:n] -= T[:n] @ xi
+    return _block_write_partials(Q[:n].T @ Q[:n], partials, k)
+
+
+def block_ortho(Q, S, state, n) -> None:
+    k = _multi_k("block_ortho", Q, S, rows=n)
+    if _block_flagged(state):
+        return
+    Q[:n] = Q[:n] @ _block_region(state, BS_ZINV, k)
+    S[:n] = Q[:n] + S[:n] @ _block_region(state, BS_ZETA, k).T
+
+
+def block_coef_alpha(partials, nblocks: int, state, k: int, kg: int,
+                     it: int) -> None:
+    if _block_flagged(state):
+        return
+    m = _block_sym(partials, nblocks, k, kg)
+    l = _block_chol(m, kg)
+    _block_region(state, BS_M, k).copy_(m)
+    if l is None:
+        state[BS_FLAG] = 1.0
+        state[BS_ITER] = float(it)
+        return
+    # column c: L y = e_c, L^T x = y (the kernel's order of operations)
+    xi = torch.eye(k, dtype=torch.float64)
+    for c in range(kg):
+        for i in range(c, kg):
+            s = 1.0 if i == c else 0.0
+            for q in range(c, i):
+                s -= float(l[i, q]) * float(xi[q, c])
+            xi[i, c] = s / float(l[i, i])
+        for i in range(kg - 1, -1, -1):
+            s = float(xi[i, c])
+            for q in range(i + 1, kg):
+                s -= float(l[q, i]) * float(xi[q, c])
+            xi[i, c] = s / float(l[i, i])
+    C = _block_region(state, BS_C, k)
+    _block_region(state, BS_XIC, k).copy_(xi @ C)
+    _block_region(state, BS_XI, k).copy_(xi)
+
+
+def block_coef_beta(partials, nblocks: int, state, rr_out, k: int, kg: int,
+                    it: int, init: bool = False) -> None:
+    if _block_flagged(state):
+        rr_out[k] = state[BS_FLAG].clone()
+        rr_out[k + 1] = state[BS_ITER].clone()
+        return
+    g = _block_sym(partials, nblocks, k, kg)
+    l = _block_chol(g, kg)
+    _block_region(state, BS_G, k).copy_(g)
+    if l is None:
+        state[BS_FLAG] = 1.0
+        state[BS_ITER] = float(it)
+        rr_out[k] = 1.0
+        rr_out[k + 1] = float(it)
+        return
+    zeta = l.T.contiguous()
+    zi = torch.eye(k, dtype=torch.float64)
+    for c in range(kg):
+        for i in range(c, -1, -1):
+            s = 1.0 if i == c else 0.0
+            for q in range(i + 1, c + 1):
+                s -= float(zeta[i, q]) * float(zi[q, c])
+            zi[i, c] = s / float(zeta[i, i])
+    C = _block_region(state, BS_C, k)
+    cn = zeta.clone() if init else _block_newc(zeta, C.clone())
+    _block_region(state, BS_ZETA, k).copy_(zeta)
+    _block_region(state, BS_ZINV, k).copy_(zi)
+    C.copy_(cn)
+    for c in range(kg):
+        rr_out[c] = float((cn[:, c] * cn[:, c]).sum())
+    rr_out[k] = 0.0
+    rr_out[k + 1] = -1.0
 
 
 def pack_gather(sendbuf, x, idx) -> None:

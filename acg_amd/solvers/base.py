@@ -46,6 +46,9 @@ class SolveResult:
     halo_msgs_sent: int = 0
     nranks: int = 1
     nouter: int = 0  # mixed-precision refinement sweeps (0 = not refined)
+    # solve_block: block iteration at which the block broke down and the
+    # columns were handed to solve_multi (0 = at initialisation, -1 = never)
+    block_breakdown: int = -1
 
     @property
     def iters_per_s(self) -> float:
@@ -150,6 +153,48 @@ def solve_multi_by_column(solve, B, X, maxits, res_atol, res_rtol) -> list:
         out.append(solve(B[:, c].contiguous(), xc, maxits=maxits,
                          res_atol=res_atol, res_rtol=res_rtol))
         X[:, c] = xc
+    return out
+
+
+def next_multi_k(kg: int, widths=(2, 4, 8)) -> int:
+    """Smallest kernel width that holds kg columns."""
+    return next(kk for kk in widths if kk >= kg)
+
+
+def block_results(solver: str, ncols: int, active: list, conv_it: list,
+                  nit: int, breakdown: int, finish: list | None, bnrm: list,
+                  rr0: list, rr: list, met, maxits: int, res_atol: float,
+                  res_rtol: float, tsolve: float, flops_per_it: float) -> list:
+    """SolveResults of one ``solve_block`` group, the same bookkeeping on
+    the CPU and the GPU.  ``active`` lists the group columns that formed
+    the block (the others had a zero initial residual), ``conv_it[c]`` the
+    block iteration at which column c first met its tolerance (None: not
+    yet), ``nit`` the block iterations run, ``rr[c]`` the last recurrence
+    residual norm squared.  After a breakdown at block iteration
+    ``breakdown`` >= 0, ``finish[i]`` is the solve_multi result of
+    ``active[i]``: its iterations are added to the block's."""
+    out = []
+    for c in range(ncols):
+        res = SolveResult(solver=solver, maxits=maxits, res_atol=res_atol,
+                          res_rtol=res_rtol, nranks=1)
+        res.bnrm2 = bnrm[c]
+        res.r0nrm2 = math.sqrt(max(rr0[c], 0.0))
+        res.tsolve = tsolve
+        fin = finish[active.index(c)] if finish is not None and c in active else None
+        if fin is not None:
+            res.block_breakdown = breakdown
+            res.converged = fin.converged
+            res.rnrm2 = fin.rnrm2
+            if conv_it[c] is not None and fin.niterations == 0:
+                res.niterations = conv_it[c]
+            else:
+                res.niterations = breakdown + fin.niterations
+        else:
+            res.rnrm2 = math.sqrt(max(rr[c], 0.0))
+            res.converged = conv_it[c] is not None or met(c, rr[c])
+            res.niterations = conv_it[c] if conv_it[c] is not None else nit
+        res.nflops = res.niterations * flops_per_it
+        out.append(res)
     return out
 
 

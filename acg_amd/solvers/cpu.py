@@ -23,7 +23,8 @@ import torch
 from ..dist.halo import HaloExchange
 from ..ops import torch_ref as ops
 from ..part.subdomain import LocalSystem
-from .base import (SolveResult, cg_flops_per_iter, check_multi_shapes, refine,
+from .base import (SolveResult, block_results, cg_flops_per_iter,
+                   check_multi_shapes, next_multi_k, refine,
                    solve_multi_by_column)
 
 
@@ -45,6 +46,7 @@ class CGSolverCPU:
         self.n = L.nowned
         self.nlocal = L.nowned + L.nghost
         self._A_vals32 = None  # fp32 copy of the matA values (solve_mixed)
+        self.multi_group = 8  # solve_block: columns per block, 2, 4 or 8
 
     # -- helpers ----------------------------------------------------------
 
@@ -148,6 +150,109 @@ class CGSolverCPU:
         check_multi_shapes(B, X, self.n, self.nlocal)
         return solve_multi_by_column(self.solve, B, X, maxits, res_atol,
                                      res_rtol)
+
+    # -- block CG (beyond reference; the oracle of CGSolverHIP.solve_block)
+
+    def solve_block(self, B: torch.Tensor, X: torch.Tensor, maxits: int = 100,
+                    res_atol: float = 0.0, res_rtol: float = 1e-9) -> list:
+        """Block CG with orthonormalised residuals for k right-hand sides,
+        serial: the algorithm, grouping (``self.multi_group``), padding,
+        removal of zero-residual columns, pivot threshold and hand-over to
+        :meth:`solve_multi` of CGSolverHIP.solve_block, driven through the
+        torch_ref ops without the host-test lag.  Several ranks and k = 1
+        fall back to :meth:`solve_multi`."""
+        k = check_multi_shapes(B, X, self.n, self.nlocal)
+        if self.multi_group not in ops.MULTI_K:
+            raise ValueError(f"multi_group must be one of {ops.MULTI_K}, "
+                             f"got {self.multi_group}")
+        serial = self.comm is None or self.comm.size == 1
+        if k == 1 or not serial or self.n == 0:
+            return self.solve_multi(B, X, maxits, res_atol, res_rtol)
+        out = []
+        for g0 in range(0, k, self.multi_group):
+            kg = min(self.multi_group, k - g0)
+            out += self._solve_block_group(B[:, g0:g0 + kg], X[:, g0:g0 + kg],
+                                           maxits, res_atol, res_rtol)
+        return out
+
+    def _spmm(self, Xm: torch.Tensor, Y: torch.Tensor) -> None:
+        for c in range(Xm.shape[1]):
+            y = self._vec()
+            self._spmv(Xm[:, c].contiguous(), y)
+            Y[:, c] = y
+
+    def _solve_block_group(self, B, X, maxits, res_atol, res_rtol) -> list:
+        n, kg0 = self.n, B.shape[1]
+        t0 = time.perf_counter()
+        T0 = torch.zeros(n, kg0, dtype=torch.float64)
+        self._spmm(X, T0)
+        R0 = B - T0
+        bnrm = [math.sqrt(float(torch.dot(B[:, c], B[:, c]))) for c in range(kg0)]
+        rr0 = [float(torch.dot(R0[:, c], R0[:, c])) for c in range(kg0)]
+        rtol2 = [max(res_atol, res_rtol * bn) ** 2 for bn in bnrm]
+        for c in range(kg0):
+            if not math.isfinite(rr0[c]):
+                raise FloatingPointError(
+                    f"block CG: initial rr={rr0[c]} in column {c}")
+
+        def met(c: int, rr: float) -> bool:
+            return rr <= rtol2[c] if rtol2[c] > 0 else rr == 0.0
+
+        conv_it: list = [0 if met(c, rr0[c]) else None for c in range(kg0)]
+        active = [c for c in range(kg0) if rr0[c] != 0.0]
+        rr = list(rr0)
+        nit, bd, finish = 0, -1, None
+        if not all(ci is not None for ci in conv_it):
+            kg = len(active)
+            K = next_multi_k(kg, ops.MULTI_K)
+
+            def mv(rows):
+                return torch.zeros(rows, K, dtype=torch.float64)
+
+            Xi, Q, T, Sm = mv(self.nlocal), mv(n), mv(n), mv(self.nlocal)
+            Xi[:, :kg] = X[:, active]
+            Q[:, :kg] = R0[:, active]
+            partials = ops.alloc_partials_multi("cpu", K)
+            state = ops.alloc_block_state("cpu")
+            rr_out = torch.zeros(K + 2, dtype=torch.float64)
+            nb = ops.gram_multi(Q, Q, partials, n=n)
+            ops.block_coef_beta(partials, nb, state, rr_out, K, kg, 0, init=True)
+            ops.block_ortho(Q, Sm, state, n)
+            if float(rr_out[K]) != 0.0:
+                bd = 0
+            while bd < 0 and nit < maxits:
+                self._spmm(Sm, T)
+                nb = ops.gram_multi(Sm, T, partials, n=n)
+                ops.block_coef_alpha(partials, nb, state, K, kg, nit + 1)
+                nb = ops.block_update(Xi, Sm, Q, T, state, partials, n)
+                ops.block_coef_beta(partials, nb, state, rr_out, K, kg, nit + 1)
+                ops.block_ortho(Q, Sm, state, n)
+                nit += 1
+                if float(rr_out[K]) != 0.0:
+                    bd = int(rr_out[K + 1])
+                    break
+                for i, c in enumerate(active):
+                    v = float(rr_out[i])
+                    if not math.isfinite(v):
+                        raise FloatingPointError(
+                            f"block CG diverged: rr={v} in column {c} at it {nit}")
+                    rr[c] = v
+                    if conv_it[c] is None and met(c, v):
+                        conv_it[c] = nit
+                if all(ci is not None for ci in conv_it):
+                    break
+            if bd >= 0:
+                Xf = Xi[:, :kg].contiguous()
+                finish = self.solve_multi(B[:, active].contiguous(), Xf,
+                                          max(maxits - bd, 0), res_atol,
+                                          res_rtol)
+                Xi[:, :kg] = Xf
+            for i, c in enumerate(active):
+                X[:, c] = Xi[:, i]
+        return block_results(
+            "cg-block", kg0, active, conv_it, nit, bd, finish, bnrm, rr0, rr,
+            met, maxits, res_atol, res_rtol, time.perf_counter() - t0,
+            cg_flops_per_iter(self.local.nnzA + self.local.nnzO, n))
 
     # -- mixed precision: fp32-stored operator + fp64 refinement (beyond
     # reference; the oracle of CGSolverHIP.solve_mixed) -------------------

@@ -33,7 +33,8 @@ import torch
 from ..dist.halo import HaloExchange
 from ..ops import gpu_ops as ops
 from ..part.subdomain import LocalSystem
-from .base import (SolveResult, cg_flops_per_iter, check_multi_shapes, refine,
+from .base import (SolveResult, block_results, cg_flops_per_iter,
+                   check_multi_shapes, next_multi_k, refine,
                    solve_multi_by_column)
 
 
@@ -849,6 +850,195 @@ class CGSolverHIP:
             out.append(res)
         self.niterations_total += nit
         return out
+
+    # -- block CG for several right-hand sides (beyond reference; opt-in,
+    # never auto-selected) -------------------------------------------------
+
+    def solve_block(self, B: torch.Tensor, X: torch.Tensor, maxits: int = 100,
+                    res_atol: float = 0.0, res_rtol: float = 1e-9) -> list:
+        """Block CG (Dubrulle's form with orthonormalised residuals, QR by
+        Cholesky-QR) for k right-hand sides: same shapes, grouping and
+        per-column tolerances as :meth:`solve_multi`, the same one SpMM per
+        iteration, but every column searches the sum of the group's Krylov
+        spaces, so ill-conditioned systems need fewer iterations.
+
+        A column whose initial residual is exactly zero is left out of the
+        block (converged at iteration 0, X column untouched).  When a
+        Cholesky pivot fails the relative test (dependent right-hand sides,
+        a column that converged exactly) the block stops where it is and
+        :meth:`solve_multi` finishes from the current X: ``block_breakdown``
+        of the results holds the block iteration of the hand-over and
+        ``niterations`` counts both parts.  Outside the fast path of
+        solve_multi, and for k = 1, this IS solve_multi."""
+        k = check_multi_shapes(B, X, self.n, self.nlocal)
+        kmax = self._multi_kmax() if self._multi_fast_path() else 0
+        if k == 1 or kmax == 0:
+            return self.solve_multi(B, X, maxits, res_atol, res_rtol)
+        out = []
+        for g0 in range(0, k, kmax):
+            kg = min(kmax, k - g0)
+            out += self._solve_block_group(B[:, g0:g0 + kg], X[:, g0:g0 + kg],
+                                           maxits, res_atol, res_rtol)
+        return out
+
+    def _block_ws(self, K: int) -> dict:
+        key = f"block{K}"
+        ws = self._ws.get(key)
+        if ws is None:
+            def mv(rows):
+                return torch.zeros(rows, K, dtype=torch.float64,
+                                   device=self.device)
+            ws = self._ws[key] = {
+                "Q": mv(self.n), "T": mv(self.n), "Bp": mv(self.n),
+                "S": mv(self.nlocal), "Xi": mv(self.nlocal),
+                "scal": ops.alloc_scalars_multi(self.device, K),
+                "partials": ops.alloc_partials_multi(self.device, K),
+                "state": ops.alloc_block_state(self.device),
+                "rr_out": torch.zeros(K + 2, dtype=torch.float64,
+                                      device=self.device),
+            }
+        return ws
+
+    def _solve_block_group(self, B, X, maxits: int, res_atol: float,
+                           res_rtol: float) -> list:
+        """One group of up to multi_group columns (eager; the lag-2 host
+        test of _solve_multi_group reads residual norms, breakdown flag and
+        iteration from one (K + 2)-double copy)."""
+        S = ops
+        n, kg0 = self.n, B.shape[1]
+        ws = self._block_ws(next_multi_k(kg0, S.MULTI_K))
+        torch.cuda.synchronize(self.device)
+        t0 = time.perf_counter()
+        # R0 = B - A X0 and the norms of the whole group
+        Bp, Xi, Q, T = ws["Bp"], ws["Xi"], ws["Q"], ws["T"]
+        scal, partials = ws["scal"], ws["partials"]
+        scal.zero_()
+        Bp.zero_()
+        Bp[:, :kg0] = B
+        Xi.zero_()
+        Xi[:, :kg0] = X
+        S.dot_multi(Bp, Bp, partials, scal, S.S_BNRM2, n=n)
+        self._spmm(Xi, T, scal, partials)
+        torch.sub(Bp, T, out=Q)
+        S.dot_multi(Q, Q, partials, scal, S.S_RR, n=n)
+        slab = scal.cpu()
+        bnrm = [math.sqrt(max(float(slab[c, S.S_BNRM2]), 0.0)) for c in range(kg0)]
+        rr0 = [float(slab[c, S.S_RR]) for c in range(kg0)]
+        rtol2 = [max(res_atol, res_rtol * bn) ** 2 for bn in bnrm]
+        for c in range(kg0):
+            if not math.isfinite(rr0[c]):
+                raise FloatingPointError(
+                    f"block CG: initial rr={rr0[c]} in column {c}")
+
+        def met(c: int, rr: float) -> bool:
+            return rr <= rtol2[c] if rtol2[c] > 0 else rr == 0.0
+
+        conv_it: list = [0 if met(c, rr0[c]) else None for c in range(kg0)]
+        active = [c for c in range(kg0) if rr0[c] != 0.0]
+        rr = list(rr0)
+        nit, bd, finish = 0, -1, None
+        if not all(ci is not None for ci in conv_it):
+            kg = len(active)
+            K = next_multi_k(kg, S.MULTI_K)
+            Ract, Xact = Q[:, active], Xi[:, active]  # copies
+            ws = self._block_ws(K)
+            Xi, Q, T, Sm = ws["Xi"], ws["Q"], ws["T"], ws["S"]
+            partials, state, rr_out = ws["partials"], ws["state"], ws["rr_out"]
+            for buf in (Xi, Q, Sm, state, rr_out):
+                buf.zero_()
+            Xi[:, :kg] = Xact
+            Q[:, :kg] = Ract
+            nit, bd = self._block_iterate(ws, K, kg, active, conv_it, rr, met,
+                                          maxits)
+            if bd >= 0:
+                Xf = Xi[:, :kg].contiguous()
+                finish = self.solve_multi(B[:, active].contiguous(), Xf,
+                                          max(maxits - bd, 0), res_atol,
+                                          res_rtol)
+                Xi[:, :kg] = Xf
+            for i, c in enumerate(active):
+                X[:, c] = Xi[:, i]
+        torch.cuda.synchronize(self.device)
+        tsolve = time.perf_counter() - t0
+        if self.prof.enabled:
+            self.prof.reset()
+        self.niterations_total += nit
+        return block_results(
+            "cg-hip-block", kg0, active, conv_it, nit, bd, finish, bnrm, rr0,
+            rr, met, maxits, res_atol, res_rtol, tsolve,
+            cg_flops_per_iter(self.local.nnzA + self.local.nnzO, n))
+
+    def _block_iterate(self, ws: dict, K: int, kg: int, active: list,
+                       conv_it: list, rr: list, met, maxits: int):
+        """The block iteration on a prepared workspace (Q = R0, S = 0,
+        state = 0).  Updates conv_it / rr of the active columns; returns
+        (block iterations run, breakdown iteration or -1)."""
+        S = ops
+        n = self.n
+        Xi, Q, T, Sm = ws["Xi"], ws["Q"], ws["T"], ws["S"]
+        partials, state, rr_out = ws["partials"], ws["state"], ws["rr_out"]
+        LAG = 2
+        hostbuf = [torch.zeros(K + 2, dtype=torch.float64, pin_memory=True)
+                   for _ in range(LAG + 1)]
+        evdone = [torch.cuda.Event() for _ in range(LAG + 1)]
+        cur = torch.cuda.current_stream(self.device)
+        bd = -1
+
+        def read(buf, it: int) -> bool:
+            """Host test of the state after block iteration ``it``; True
+            when the group is finished (all met, or breakdown)."""
+            nonlocal bd
+            if float(buf[K]) != 0.0:
+                bd = int(buf[K + 1])
+                return True
+            for i, c in enumerate(active):
+                v = float(buf[i])
+                if not math.isfinite(v):
+                    raise FloatingPointError(
+                        f"block CG diverged: rr={v} in column {c} at it {it}")
+                rr[c] = v
+                if conv_it[c] is None and met(c, v):
+                    conv_it[c] = it
+            return all(ci is not None for ci in conv_it)
+
+        # start-up: Q <- R0 zeta^-1, C = zeta, S = Q
+        with self.prof.span("block_init"):
+            nb = S.gram_multi(Q, Q, partials, n=n)
+            S.block_coef_beta(partials, nb, state, rr_out, K, kg, 0, init=True)
+            S.block_ortho(Q, Sm, state, n)
+        if float(rr_out.cpu()[K]) != 0.0:
+            return 0, 0
+
+        def check(j: int) -> bool:
+            evdone[j % (LAG + 1)].synchronize()
+            return read(hostbuf[j % (LAG + 1)], j + 1)
+
+        nit = 0
+        done = False
+        while not done and nit < maxits:
+            if nit >= LAG and check(nit - LAG):
+                done = True
+                break
+            with self.prof.span("spmvA"):
+                self._spmm(Sm, T, None, None)
+            with self.prof.span("block_gram"):
+                nb = S.gram_multi(Sm, T, partials, n=n)
+                S.block_coef_alpha(partials, nb, state, K, kg, nit + 1)
+            with self.prof.span("block_update"):
+                nb = S.block_update(Xi, Sm, Q, T, state, partials, n)
+                S.block_coef_beta(partials, nb, state, rr_out, K, kg, nit + 1)
+            with self.prof.span("block_ortho"):
+                S.block_ortho(Q, Sm, state, n)
+            j = nit % (LAG + 1)
+            hostbuf[j].copy_(rr_out, non_blocking=True)
+            evdone[j].record(cur)
+            nit += 1
+        if not done:
+            for j in range(max(nit - LAG, 0), nit):
+                if check(j):
+                    break
+        torch.cuda.synchronize(self.device)
+        return nit, bd
 
     # -- mixed precision: fp32-stored operator + fp64 refinement (beyond
     # reference; opt-in, no auto-selection) -------------------------------

@@ -422,8 +422,54 @@ def cg_device(sellptr: torch.Tensor, cols: torch.Tensor, vals: torch.Tensor,
     (per-XCD then global) grid barrier; default = env ACG_DEVCG_HIER
     ("auto": hierarchical from 64 blocks up -- measured crossover,
     tools/devcg_barrier_ab.py).  Returns the grid size used."""
+    what = "cg_device"
     nslices = sellptr.numel() - 1
-    assert barrier_state.numel() >= BAR_STATE_WORDS
+    if sellptr.dtype != torch.int64 or nslices < 1:
+        raise ValueError(f"{what}: sellptr must be int64 with at least 2 "
+                         f"entries, got {sellptr.dtype}[{sellptr.numel()}]")
+    if cols.dtype not in (torch.int32, torch.int64):
+        raise ValueError(f"{what}: cols must be int32 or int64, got {cols.dtype}")
+    if vals.dtype != torch.float64:
+        raise ValueError(f"{what}: operator values must be float64, got "
+                         f"{vals.dtype} (the fp32-stored operator is not supported)")
+    nrows, maxits = int(nrows), int(maxits)
+    if not 0 < nrows <= nslices * 64:
+        raise ValueError(f"{what}: nrows={nrows} does not fit {nslices} slices")
+    # sellptr[-1] lives on the device: reading it would cost a sync
+    if cols.numel() != vals.numel():
+        raise ValueError(f"{what}: cols and vals differ in length: "
+                         f"{cols.numel()} vs {vals.numel()}")
+    for nm, v in (("b", b), ("x", x), ("r", r), ("p", p), ("t", t)):
+        if (v.dtype != torch.float64 or not v.is_contiguous()
+                or v.numel() < nrows):
+            raise ValueError(f"{what}: {nm} must be a contiguous float64 "
+                             f"vector of at least {nrows} elements")
+    for nm, v, need in (("scal", scal, S_NSLOTS), ("partials", partials, MAXG)):
+        if (v.dtype != torch.float64 or not v.is_contiguous()
+                or v.numel() < need):
+            raise ValueError(f"{what}: {nm} must be contiguous float64 with "
+                             f"at least {need} elements")
+    if (out2.dtype != torch.int32 or not out2.is_contiguous()
+            or out2.numel() < 2):
+        raise ValueError(f"{what}: out2 must be contiguous int32 with at "
+                         "least 2 elements")
+    if (barrier_state.dtype not in (torch.int32, torch.uint32)
+            or not barrier_state.is_contiguous()
+            or barrier_state.numel() < BAR_STATE_WORDS):
+        raise ValueError(f"{what}: barrier_state must hold at least "
+                         f"{BAR_STATE_WORDS} contiguous 4-byte integer words")
+    for nm, v in (("sellptr", sellptr), ("cols", cols), ("vals", vals),
+                  ("b", b), ("x", x), ("r", r), ("p", p), ("t", t),
+                  ("scal", scal), ("partials", partials), ("out2", out2),
+                  ("barrier_state", barrier_state)):
+        if not v.is_cuda or v.device != x.device:
+            raise ValueError(f"{what}: {nm} must live on the GPU of x, got "
+                             f"{v.device}")
+    if not cols.is_contiguous() or not vals.is_contiguous() \
+            or not sellptr.is_contiguous():
+        raise ValueError(f"{what}: sellptr, cols and vals must be contiguous")
+    if maxits < 0:
+        raise ValueError(f"{what}: maxits must not be negative, got {maxits}")
     if hier is None:
         import os
 

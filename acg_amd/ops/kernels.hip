@@ -1683,7 +1683,9 @@ k_cg_device(long nslices, long nrows,
         grid_sum(acc, S_RR);
         if (!alive) break;
         const double rr_new = scal[S_RR];
-        const double beta = rr_new / rr;
+        // 0/0-safe like every other CG path: b = 0, or a residual that has
+        // underflowed to exact 0, freezes the iterate instead of NaN-ing p
+        const double beta = safe_div(rr_new, rr);
         for (long i = tid; i < nrows; i += nth)
             st_sc1_f64(p + i, beta * p[i] + r[i]);
         rr = rr_new;

@@ -629,6 +629,60 @@ def pipelined_finalize(partials, nblocks: int, scal, first: bool) -> None:
     scal[S_DELTA] = d
 
 
+BAR_STATE_WORDS = 400  # same as gpu_ops; the reference needs no barrier
+
+
+def cg_device(sellptr, cols, vals, nrows: int, b, x, r, p, t, scal, partials,
+              out2, barrier_state, maxits: int, res_atol: float,
+              res_rtol: float, hier=None) -> int:
+    """Whole classic CG solve in one call (matches k_cg_device): bnrm2 =
+    (b,b); r = p = b - A x; then alpha = rr/(p,t), x += alpha p,
+    r -= alpha t, beta = rr'/rr, p = beta p + r until rr <= max(atol,
+    rtol*|b|)^2 or ``maxits`` steps.  Publishes (b,b), (r0,r0), the last
+    (p,t) and the final (r,r) in S_BNRM2, S_RR_PREV, S_PT and S_RR, and
+    (niterations, converged) in ``out2``.  Every 256 rows form a block whose
+    partial sum of the last reduction is left in ``partials`` when that has
+    room; returns the number of blocks."""
+    if vals.dtype != torch.float64:
+        raise ValueError(f"cg_device: operator values must be float64, got {vals.dtype}")
+    nslices = sellptr.numel() - 1
+    n = nrows
+    grid = (nslices * 64 + 255) // 256
+
+    def gsum(v, slot):
+        part = torch.stack([v[i:i + 256].sum() for i in range(0, grid * 256, 256)])
+        if partials.numel() >= grid:
+            partials[:grid] = part
+        scal[slot] = part.sum()
+
+    gsum(b[:n] * b[:n], S_BNRM2)
+    spmv_sell(sellptr, cols, vals, n, x, t)
+    r[:n] = b[:n] - t[:n]
+    p[:n] = r[:n]
+    gsum(r[:n] * r[:n], S_RR)
+    scal[S_RR_PREV] = scal[S_RR].clone()
+    rr = float(scal[S_RR])
+    rt = max(res_rtol * math.sqrt(float(scal[S_BNRM2])), res_atol)
+    rtol2 = rt * rt
+    k = 0
+    converged = rtol2 > 0.0 and rr <= rtol2
+    while not converged and k < maxits:
+        spmv_sell(sellptr, cols, vals, n, p, t)
+        gsum(p[:n] * t[:n], S_PT)
+        alpha = _sdiv(rr, float(scal[S_PT]))
+        r[:n] -= alpha * t[:n]
+        x[:n] += alpha * p[:n]
+        gsum(r[:n] * r[:n], S_RR)
+        rr_new = float(scal[S_RR])
+        p[:n] = _sdiv(rr_new, rr) * p[:n] + r[:n]
+        rr = rr_new
+        k += 1
+        converged = rtol2 > 0.0 and rr <= rtol2
+    out2[0] = k
+    out2[1] = 1 if converged else 0
+    return grid
+
+
 # ---------------------------------------------------------------------------
 # Multiple right-hand sides (same layout as gpu_ops: (n, K) multivectors,
 # (K, S_NSLOTS) slab, (K, MAXG) partials).  Every column is computed by the

@@ -1150,11 +1150,15 @@ class CGSolverHIP:
         S = ops
         res.bnrm2 = math.sqrt(max(float(self.scal[S.S_BNRM2]), 0.0))
         res.r0nrm2 = math.sqrt(max(float(self.scal[S.S_RR_PREV]), 0.0))
-        res.rnrm2 = math.sqrt(max(float(self.scal[S.S_RR]), 0.0))
+        rr = float(self.scal[S.S_RR])
+        res.rnrm2 = math.sqrt(max(rr, 0.0))
         res.niterations = int(out2[0])
         conv = int(out2[1])
         if conv < 0:
             raise RuntimeError("device CG grid barrier timed out (residency?)")
+        if not math.isfinite(rr):
+            raise FloatingPointError(
+                f"CG diverged: rr={rr} at it {res.niterations}")
         res.converged = bool(conv)
         nnz_full = self.local.nnzA + self.local.nnzO
         res.nflops = res.niterations * cg_flops_per_iter(nnz_full, n)

@@ -1354,3 +1354,283 @@ def check_partials(got, halves):
     assert np.all(np.isfinite(part[:nb]))
     if halves == 2:
         assert np.all(np.isfinite(part[MAXG:MAXG + nb]))
+
+
+# ---------------------------------------------------------------------------
+# the one-launch device CG (k_cg_device): case, step-chained expectations,
+# runner and the check procedures the CPU (torch_ref, mutants) and GPU tests
+# share
+
+BAR_STATE_WORDS = 400
+OUT2_SENTINEL = (-7, -9)
+DEVCG_KS = (0, 1, 2, 3)
+
+
+def device_cg_blocks(nslices):
+    """Blocks the launcher asks for before the residency cap."""
+    return sell_blocks(nslices)
+
+
+def device_cg_case(nslices, zero_b=False, zero_x0=False):
+    """Symmetric, strictly diagonally dominant system (diagonal >= 2x the
+    absolute off-diagonal row sum: Jacobi-scaled spectrum in [1/2, 3/2]) of
+    nslices*64 - 13 rows.  The 64-row slices cycle through three classes of
+    row length (the diagonal included): at most 3 (only the remainder loop
+    of the 4-way unrolled SpMV runs), 5..7 (one unrolled trip and a
+    remainder) and up to 13 (several trips).  Couplings stay inside a class:
+    neighbours in the same slice, and rows 192 and 384 further on, which
+    belong to other 256-thread blocks."""
+    rng = np.random.default_rng(8000 + nslices)
+    n = nslices * C - 13
+    i = np.arange(n, dtype=np.int64)
+    lane = i % C
+    cls = ((i // C) + nslices) % 3
+    ei, ej = [], []
+
+    def link(mask, d):
+        m = mask & (i + d < n) & (rng.random(n) < 0.7)
+        ei.append(i[m])
+        ej.append(i[m] + d)
+
+    link((cls == 0) & (lane % 2 == 0) & (lane < 32), 1)
+    link((cls == 0) & (lane >= 32), 3 * C)
+    for d in (1, 2):
+        link((cls == 1) & (lane + d < C), d)
+    link(cls == 1, 3 * C)
+    for d in (1, 2, 3, 5):
+        link((cls == 2) & (lane + d < C), d)
+    for d in (3 * C, 6 * C):
+        link(cls == 2, d)
+    ei, ej = np.concatenate(ei), np.concatenate(ej)
+    w = rng.uniform(0.5, 2.0, size=len(ei)) * rng.choice([-1.0, 1.0], size=len(ei))
+    off = (np.bincount(ei, np.abs(w), minlength=n)
+           + np.bincount(ej, np.abs(w), minlength=n))
+    diag = 2.0 * off * rng.uniform(1.0, 1.25, size=n) + rng.uniform(0.5, 2.0, size=n)
+    assert np.all(diag >= 2.0 * off) and np.all(diag > 0)
+    rows = np.concatenate([ei, ej, i])
+    cols = np.concatenate([ej, ei, i])
+    vals = np.concatenate([w, w, diag])
+    order = np.lexsort((cols, rows))
+    rows, cols, vals = rows[order], cols[order], vals[order]
+    rowptr = np.zeros(n + 1, dtype=np.int64)
+    np.cumsum(np.bincount(rows, minlength=n), out=rowptr[1:])
+    L = sell_padded_len(rowptr)
+    per_slice = L[::C]
+    if nslices >= 3:
+        assert (per_slice < 4).any() and (per_slice % 4 != 0).any() \
+            and (per_slice >= 8).any(), "a row-length class is missing"
+    else:
+        assert (per_slice > 4).any() and (per_slice % 4 != 0).any()
+    rv = lambda: rng.uniform(0.5, 2.0, size=n) * rng.choice([-1.0, 1.0], size=n)
+    b, x0 = rv(), rv()
+    return SimpleNamespace(nslices=nslices, nrows=n, ncols=n, rowptr=rowptr,
+                           cols=cols, vals=vals, L=L,
+                           b=np.zeros(n) if zero_b else b,
+                           x0=np.zeros(n) if zero_x0 else x0,
+                           _hp=None, _packed={}, _dev={}, _expect={})
+
+
+def _devcg_spmv(case, x, xM):
+    """A x and |A| xM by row (sorted CSR without empty rows: one reduceat)."""
+    if case._hp is None:
+        case._hp = hp(case.vals)
+    a, starts = case._hp, case.rowptr[:-1]
+    return (np.add.reduceat(a * x[case.cols], starts),
+            np.add.reduceat(habs(a) * xM[case.cols], starts))
+
+
+def device_cg_init_expect(case):
+    """The maxits = 0 launch.  t = A x0 carries L products per row; r0 =
+    fl(b - t) adds one rounding, relative to |r0| <= |b| + |A||x0|, so it
+    stays within (L + 48) u (|b| + |A||x0|) of the exact b - A x0."""
+    if "init" in case._expect:
+        return case._expect["init"]
+    e = Expect("k_cg_device/init")
+    xh, bh = hp(case.x0), hp(case.b)
+    t, Mt = _devcg_spmv(case, xh, habs(xh))
+    r, Mr = bh - t, habs(bh) + Mt
+    e.add("t", t, Mt, case.L)
+    e.add("r", r, Mr, case.L)
+    e.add_same("p", "r")
+    e.add_exact("x", case.x0)
+    bn, bntol = dot(bh, bh)
+    rr, rrtol = dot(r, r, ta=bound(Mr, case.L), tb=bound(Mr, case.L))
+    e.add_tol(f"scal{S_BNRM2}", bn, bntol)
+    e.add_tol(f"scal{S_RR}", rr, rrtol)
+    e.add_same(f"scal{S_RR_PREV}", f"scal{S_RR}")
+    e.scalars(SENTINELS, touched=(S_RR, S_PT, S_RR_PREV, S_BNRM2))
+    e.add_exact(f"scal{S_PT}", SENTINELS[S_PT])
+    case._expect["init"] = e
+    return e
+
+
+_DEVCG_STATE = ("x", "r", "p", f"scal{S_RR}")
+_DEVCG_REPORTED = ("t", "r", f"scal{S_PT}", f"scal{S_RR}")
+
+
+def device_cg_step_expect(case, state, reported, k=None):
+    """One CG step from EXACTLY the fp64 state (x_k, r_k, p_k, rr_k) that
+    the ``maxits = k`` launch returned, for the ``maxits = k + 1`` launch
+    (``reported``), which repeats the first k steps bit for bit.
+
+    No error bound is carried from step to step, and none through the
+    coefficients either: the kernel publishes every value that the next
+    stage of a step reads back from memory -- t, (p,t), the new r and the
+    new (r,r) -- so each stage is compared with the high-precision result
+    of ITS inputs as the kernel reports them, and each reported value is
+    itself checked against the stage before:
+
+      t      = A p_k                   L products per row
+      (p,t)  = (p_k, A p_k)            dot()'s propagated tolerance
+      alpha  = rr_k / (p,t)'           1 rounding
+      r      = r_k - alpha t'          alpha, product, sum: 3 roundings
+      x      = x_k + alpha p_k         3 roundings
+      (r,r)  from that r               dot()'s propagated tolerance
+      beta   = (r,r)' / rr_k           1 rounding (safe_div: 0 when rr_k = 0)
+      p      = beta p_k + r'           3 roundings
+
+    (primes: as reported).  Each rounding is relative to a partial result
+    bounded by the magnitude M, so 3 u M (1 + O(u)) is far inside the
+    module's 48 u M; no constant is added."""
+    bits = [np.asarray(state[k_], np.float64).tobytes() for k_ in _DEVCG_STATE] \
+        + [np.asarray(reported[k_], np.float64).tobytes() for k_ in _DEVCG_REPORTED]
+    hit = case._expect.get(("step", k))
+    if k is not None and hit is not None and hit[0] == bits:
+        return hit[1]
+    e = Expect("k_cg_device/step")
+    xk, rk, pk = hp(state["x"]), hp(state["r"]), hp(state["p"])
+    rrk = float(state[f"scal{S_RR}"][0])
+    t, Mt = _devcg_spmv(case, pk, habs(pk))
+    e.add("t", t, Mt, case.L)
+    pt, pttol = dot(pk, t, tb=bound(Mt, case.L))
+    e.add_tol(f"scal{S_PT}", pt, pttol)
+    alpha = ratio_coeff(rrk, float(reported[f"scal{S_PT}"][0]))
+    aa = abs(alpha)
+    tr = hp(reported["t"])
+    r, Mr = rk - alpha * tr, habs(rk) + aa * habs(tr)
+    e.add("r", r, Mr)
+    e.add("x", xk + alpha * pk, habs(xk) + aa * habs(pk))
+    rr, rrtol = dot(r, r, ta=bound(Mr), tb=bound(Mr))
+    e.add_tol(f"scal{S_RR}", rr, rrtol)
+    beta = ratio_coeff(float(reported[f"scal{S_RR}"][0]), rrk)
+    rn = hp(reported["r"])
+    e.add("p", beta * pk + rn, abs(beta) * habs(pk) + habs(rn))
+    if k is not None:
+        case._expect[("step", k)] = (bits, e)
+    return e
+
+
+def run_device_cg(ops, case, dev, *, maxits, atol=0.0, rtol=0.0, hier=None,
+                  col64=False):
+    """One launch on poisoned buffers and a freshly zeroed barrier state;
+    returns every output plus the grid cg_device reports."""
+    import torch
+
+    from acg_amd.ops import torch_ref
+
+    if col64 not in case._packed:
+        case._packed[col64] = torch_ref.sell_from_csr(
+            case.rowptr, case.cols.astype(np.int64 if col64 else np.int32),
+            case.vals)
+    key = (str(dev), col64)
+    if key not in case._dev:
+        case._dev[key] = tuple(_t(a, dev) for a in case._packed[col64])
+    sp, sc, sv = case._dev[key]
+    n = case.nrows
+    x = _t(case.x0, dev)
+    r, p, t = _nan(n, dev), _nan(n, dev), _nan(n, dev)
+    scal = _t(SENTINELS, dev)
+    partials = _nan(2 * MAXG, dev)
+    out2 = torch.tensor(OUT2_SENTINEL, dtype=torch.int32, device=dev)
+    bar = torch.zeros(BAR_STATE_WORDS, dtype=torch.int32, device=dev)
+    grid = ops.cg_device(sp, sc, sv, n, _t(case.b, dev), x, r, p, t, scal,
+                         partials, out2, bar, maxits, atol, rtol, hier=hier)
+    got = {"x": _np(x), "r": _np(r), "p": _np(p), "t": _np(t),
+           "out2": _np(out2), "grid": int(grid)}
+    _partials_out(got, partials, int(grid))
+    return _scal_out(got, scal)
+
+
+DEVCG_BITWISE = ("x", "r", "p", "t", "out2") + tuple(f"scal{i}" for i in range(S_NSLOTS))
+
+
+def device_cg_same_bits(a, b, names=DEVCG_BITWISE):
+    """Names whose bits differ between two launches' outputs."""
+    return [k for k in names
+            if not np.array_equal(np.ascontiguousarray(a[k]).view(np.uint8),
+                                  np.ascontiguousarray(b[k]).view(np.uint8))]
+
+
+def device_cg_check_every_k(got, got0, k, converged=0):
+    """What holds after any launch that ran k steps."""
+    assert got["out2"].tolist() == [k, converged], (got["out2"], k, converged)
+    for slot in (S_BNRM2, S_RR_PREV):
+        assert _bits_equal(got[f"scal{slot}"], got0[f"scal{slot}"]), \
+            f"slot {slot} differs from the maxits=0 launch at k={k}"
+    for slot in (S_GAMMA, S_DELTA, S_GAMMA_PREV, S_ALPHA_PREV):
+        assert _bits_equal(got[f"scal{slot}"], SENTINELS[slot]), f"slot {slot} written"
+    check_partials(got, halves=1)
+
+
+def device_cg_check_chain(launch, case, ks=DEVCG_KS, tag=""):
+    """Init check, the per-launch invariants and the chained step k -> k+1
+    for every k in ``ks``.  ``launch(maxits=...)`` -> got (zero
+    tolerances).  Returns {maxits: got}."""
+    ms = sorted({0} | set(ks) | {k + 1 for k in ks})
+    gots = {m: launch(maxits=m) for m in ms}
+    assert_accepts(device_cg_init_expect(case), gots[0], f"{tag} init")
+    for m in ms:
+        device_cg_check_every_k(gots[m], gots[0], m)
+    for k in ks:
+        e = device_cg_step_expect(case, gots[k], gots[k + 1], k)
+        assert_accepts(e, gots[k + 1], f"{tag} step {k}->{k + 1}")
+    return gots
+
+
+def device_cg_check_tolerances(launch, case, gots):
+    """max(atol, rtol*|b|) selection, the (niterations, converged) pair and
+    the early exit, against the zero-tolerance launches ``gots`` (0..6).
+    ``launch(maxits=, atol=, rtol=)`` -> got."""
+    rr = [float(gots[m][f"scal{S_RR}"][0]) for m in range(7)]
+    bnrm = float(np.sqrt(gots[0][f"scal{S_BNRM2}"][0]))
+    assert bnrm > 0
+    for j0 in (2, 4):
+        lo, hi = np.sqrt(rr[j0]), np.sqrt(rr[j0 - 1])
+        thr = float(np.sqrt(lo * hi))
+        if not 0 < lo < thr < hi:  # the case is unfit, not the code wrong
+            raise ValueError(f"(r,r) does not fall from step {j0 - 1} to {j0}")
+        j = next(m for m in range(7) if rr[m] <= thr * thr)
+        if j < 1:
+            raise ValueError("threshold already met by x0")
+        for atol, rtol in ((thr, 0.0), (0.0, thr / bnrm),
+                           (thr, 0.5 * thr / bnrm), (0.5 * thr, thr / bnrm)):
+            got = launch(maxits=20, atol=atol, rtol=rtol)
+            device_cg_check_every_k(got, gots[0], j, converged=1)
+            diff = device_cg_same_bits(got, gots[j], DEVCG_BITWISE[:4] + DEVCG_BITWISE[5:])
+            assert not diff, f"atol={atol} rtol={rtol}: {diff} differ from maxits={j}"
+        for atol, rtol in ((thr, 0.0), (0.0, thr / bnrm)):
+            got = launch(maxits=j, atol=atol, rtol=rtol)
+            device_cg_check_every_k(got, gots[0], j, converged=1)
+            got = launch(maxits=j - 1, atol=atol, rtol=rtol)
+            device_cg_check_every_k(got, gots[0], j - 1, converged=0)
+            assert not device_cg_same_bits(got, gots[j - 1], ("x", "r", "p", "t"))
+    for atol, rtol in ((2.0 * np.sqrt(rr[0]), 0.0), (0.0, 2.0 * np.sqrt(rr[0]) / bnrm)):
+        got = launch(maxits=20, atol=float(atol), rtol=float(rtol))
+        device_cg_check_every_k(got, gots[0], 0, converged=1)
+        assert _bits_equal(got["x"], case.x0), "x touched although x0 is within tolerance"
+        assert not device_cg_same_bits(got, gots[0], ("r", "p", "t"))
+
+
+def device_cg_check_zero(launch, case):
+    """b = 0, x0 = 0: (r,r) = (p,t) = 0 from the start; both coefficient
+    divisions are 0/0 and must give 0, freezing x at 0.  ``converged``
+    follows the host rule rtol2 > 0 and rr <= rtol2 -- here rtol2 = 0."""
+    assert not case.b.any() and not case.x0.any()
+    for atol, rtol in ((0.0, 1e-9), (0.0, 0.0)):
+        got = launch(maxits=5, atol=atol, rtol=rtol)
+        for k in ("x", "r", "p", "t"):
+            assert np.all(np.isfinite(got[k])), f"{k} not finite (rtol={rtol})"
+        assert not got["x"].any(), "x moved away from 0"
+        for slot in (S_RR, S_PT, S_RR_PREV, S_BNRM2):
+            assert got[f"scal{slot}"][0] == 0.0, (slot, got[f"scal{slot}"])
+        assert got["out2"].tolist() == [5, 0], got["out2"]

@@ -394,7 +394,7 @@ def test_classic_daypx_fold_matches_unfolded(problem):
     np.testing.assert_array_equal(xf, xf2)  # fold path deterministic
 
 
-@pytest.mark.parametrize("method", ["solve", "solve_pipelined"])
+@pytest.mark.parametrize("method", ["solve", "solve_pipelined", "solve_device"])
 def test_gpu_solver_survives_residual_underflow(problem, method):
     """rtol=0 driven ~1600 iterations past convergence: the recursion
     residual underflows to exact 0 (measured ~0.5x/iteration decay) and
@@ -417,6 +417,63 @@ def test_gpu_solver_survives_residual_underflow(problem, method):
     # classic floors at ~1e-15; pipelined's recursion drift leaves the
     # frozen iterate at ~1e-12 true residual (textbook behaviour)
     assert rel < 1e-10, rel
+    if method == "solve_device":
+        # the one-launch solve reports the recursion's (r,r): exact 0 by now
+        assert res.rnrm2 == 0.0 and not res.converged
+
+
+def test_device_cg_after_other_solvers(problem):
+    """solve_pipelined leaves slots 4..7 of the scalar slab and the
+    partials scratch dirty; the one-launch solve on the same solver must
+    not read any of it: bitwise the x of a repeat and of a fresh solver."""
+    from acg_amd.solvers.hip import CGSolverHIP
+
+    A, S = problem
+    rng = np.random.default_rng(43)
+    b = torch.from_numpy(rng.standard_normal(S.nowned)).cuda()
+
+    def run(fn):
+        x = torch.zeros(S.nowned + S.nghost, dtype=torch.float64, device="cuda")
+        r = fn(b, x, maxits=60, res_rtol=0.0)
+        assert r.niterations == 60 and not r.converged
+        return x[:S.nowned].cpu().numpy(), r
+
+    solver = CGSolverHIP(S, device="cuda:0")
+    run(solver.solve_pipelined)
+    assert float(solver.scal[4:8].abs().min()) > 0  # really dirty
+    x1, r1 = run(solver.solve_device)
+    x2, r2 = run(solver.solve_device)
+    x3, r3 = run(CGSolverHIP(S, device="cuda:0").solve_device)
+    assert np.all(np.isfinite(x1)) and np.abs(x1).max() > 0
+    np.testing.assert_array_equal(x1, x2)
+    np.testing.assert_array_equal(x1, x3)
+    assert r1.rnrm2 == r2.rnrm2 == r3.rnrm2 and r1.r0nrm2 == r3.r0nrm2
+
+
+def test_device_cg_nonzero_x0(problem):
+    """The one-launch solve from x0 != 0: r0 = b - A x0 is what it reports
+    and iterates on, and it lands where the classic solver lands."""
+    from acg_amd.solvers.hip import CGSolverHIP
+
+    A, S = problem
+    rng = np.random.default_rng(47)
+    b = torch.from_numpy(rng.standard_normal(S.nowned)).cuda()
+    x0 = torch.from_numpy(rng.standard_normal(S.nowned + S.nghost)).cuda()
+    solver = CGSolverHIP(S, device="cuda:0")
+    t = torch.zeros(S.nowned, dtype=torch.float64, device="cuda")
+    solver._spmv_overlapped(x0.clone(), t)
+    r0 = float(torch.linalg.norm(b - t))
+    xd, xc = x0.clone(), x0.clone()
+    rd = solver.solve_device(b, xd, maxits=400, res_rtol=1e-10)
+    rc = solver.solve(b, xc, maxits=400, res_rtol=1e-10)
+    assert rd.converged and rc.converged, (rd.summary(), rc.summary())
+    assert abs(rd.r0nrm2 - r0) <= 1e-12 * r0, (rd.r0nrm2, r0)
+    assert rd.niterations > 5
+    assert abs(rd.niterations - rc.niterations) <= 2
+    torch.testing.assert_close(xd[:S.nowned], xc[:S.nowned], rtol=1e-7, atol=1e-9)
+    solver._spmv_overlapped(xd, t)
+    rel = float(torch.linalg.norm(b - t) / torch.linalg.norm(b))
+    assert rel < 1e-9, rel
 
 
 @pytest.mark.parametrize("solver_name", ["acg", "acg-pipelined", "acg-device", "acg-jacobi"])

@@ -220,15 +220,15 @@ def test_ref_vector_ops(n):
 
 
 def test_every_gpu_op_has_a_reference():
-    """gpu_ops and torch_ref expose the same operations (the monolithic
-    device CG and host-side prep aside)."""
+    """gpu_ops and torch_ref expose the same operations (host-side prep
+    aside)."""
     import ast
     from pathlib import Path
 
     src = Path(torch_ref.__file__).with_name("gpu_ops.py").read_text()
     ops = {n.name for n in ast.parse(src).body
            if isinstance(n, ast.FunctionDef) and not n.name.startswith("_")}
-    ops -= {"cg_device", "pick_lanes", "build_row_bins", "build_sellcsr_hybrid"}
+    ops -= {"pick_lanes", "build_row_bins", "build_sellcsr_hybrid"}
     missing = sorted(o for o in ops if not hasattr(torch_ref, o))
     assert not missing, missing
 
@@ -448,3 +448,126 @@ def test_bound_rejects_one_dropped_entry():
     assert ko.accepts(e, got)
     got["y"][i] = y[i] + 1e-11
     assert not ko.accepts(e, got)
+
+
+# ---------------------------------------------------------------------------
+# the one-launch device CG: reference vs the step-chained oracle, and mutants
+
+DEVCG_SLICES = (1, 5, 28, 33)
+DEVCG_MUTANTS = ("stale_p", "drop_pt", "drop_rr", "alpha_rr", "beta_inv",
+                 "p_old_r", "x_from_t", "rotate_prev", "touch_x", "conv_rt")
+
+
+@lru_cache(maxsize=None)
+def _devcg(nslices):
+    return ko.device_cg_case(nslices)
+
+
+def _ref_launch(case):
+    return lambda **kw: ko.run_device_cg(torch_ref, case, CPU, **kw)
+
+
+def _devcg_check_all(launch, case):
+    gots = ko.device_cg_check_chain(launch, case, ks=(0, 1, 2, 3, 4, 5))
+    ko.device_cg_check_tolerances(launch, case, gots)
+
+
+@pytest.mark.parametrize("nslices", DEVCG_SLICES)
+def test_ref_cg_device(nslices):
+    """torch_ref.cg_device passes the init check, the chained steps k = 0..4
+    (and 5, which the tolerance checks need) and the tolerance checks."""
+    case = _devcg(nslices)
+    _devcg_check_all(_ref_launch(case), case)
+    got = _ref_launch(case)(maxits=3)
+    assert got["grid"] == ko.device_cg_blocks(nslices)
+    assert got["grid"] == {1: 1, 5: 2, 28: 7, 33: 9}[nslices]
+
+
+def test_ref_cg_device_col64_zero_rhs_and_fp32_refusal():
+    case = _devcg(5)
+    a = ko.run_device_cg(torch_ref, case, CPU, maxits=4)
+    b = ko.run_device_cg(torch_ref, case, CPU, maxits=4, col64=True)
+    assert not ko.device_cg_same_bits(a, b)
+    zero = ko.device_cg_case(5, zero_b=True, zero_x0=True)
+    ko.device_cg_check_zero(_ref_launch(zero), zero)
+    sp, sc, sv = (torch.from_numpy(a) for a in case._packed[False])
+    v = torch.zeros(case.nrows, dtype=torch.float64)
+    with pytest.raises(ValueError, match="float64"):
+        torch_ref.cg_device(sp, sc, sv.float(), case.nrows, v, v, v, v, v,
+                            torch_ref.alloc_scalars(), torch_ref.alloc_partials(),
+                            torch.zeros(2, dtype=torch.int32), None, 1, 0.0, 0.0)
+
+
+def _emulate_device_cg(case, mutant=None, *, maxits, atol=0.0, rtol=0.0):
+    """fp64 emulation of k_cg_device on a grid of ceil(nslices/4) blocks of
+    256 rows, with one defect switched on.  Memory a defect reads without
+    having written it holds zeros."""
+    n = case.nrows
+    grid = ko.device_cg_blocks(case.nslices)
+    last = slice((grid - 1) * 256, n)
+    A = (case.rowptr, case.cols, case.vals)
+    scal = ko.SENTINELS.copy()
+    partials = np.full(2 * ko.MAXG, np.nan)
+
+    def gsum(v, slot, drop=False):
+        part = np.add.reduceat(v, np.arange(0, n, 256))
+        assert len(part) == grid
+        partials[:grid] = part
+        scal[slot] = part[:-1].sum() if drop else part.sum()
+
+    b, x = case.b, case.x0.copy()
+    gsum(b * b, ko.S_BNRM2)
+    t = _csr_mv(A, x)
+    r = b - t
+    p = r.copy()
+    if mutant == "touch_x":
+        x[-1] = np.nextafter(x[-1], np.inf)
+    gsum(r * r, ko.S_RR)
+    scal[ko.S_RR_PREV] = scal[ko.S_RR]
+    rr = scal[ko.S_RR]
+    rr_stale = scal[ko.S_BNRM2]
+    rt = max(rtol * np.sqrt(scal[ko.S_BNRM2]), atol)
+    rtol2 = rt if mutant == "conv_rt" else rt * rt
+    p_prev = np.zeros(n)
+    sdiv = lambda a, d: a / d if d != 0.0 else 0.0
+    k, converged = 0, bool(rtol2 > 0.0 and rr <= rtol2)
+    while not converged and k < maxits:
+        t = _csr_mv(A, p)
+        if mutant == "stale_p":  # the last block gathered last iteration's p
+            t[last] = _csr_mv(A, p_prev)[last]
+        gsum(p * t, ko.S_PT, drop=mutant == "drop_pt")
+        alpha = sdiv(rr_stale if mutant == "alpha_rr" else rr, scal[ko.S_PT])
+        r_old = r
+        r = r - alpha * t
+        x = x + alpha * (t if mutant == "x_from_t" else p)
+        gsum(r * r, ko.S_RR, drop=mutant == "drop_rr")
+        rr_new = scal[ko.S_RR]
+        beta = sdiv(rr, rr_new) if mutant == "beta_inv" else sdiv(rr_new, rr)
+        p_prev = p
+        p = beta * p + (r_old if mutant == "p_old_r" else r)
+        if mutant == "rotate_prev":
+            scal[ko.S_RR_PREV] = rr
+        rr_stale, rr = rr, rr_new
+        k += 1
+        converged = bool(rtol2 > 0.0 and rr <= rtol2)
+    got = {"x": x, "r": r, "p": p, "t": t, "grid": grid, "partials": partials,
+           "nblocks": grid, "out2": np.array([k, int(converged)], dtype=np.int32)}
+    for i in range(ko.S_NSLOTS):
+        got[f"scal{i}"] = scal[i:i + 1].copy()
+    return got
+
+
+@pytest.mark.parametrize("nslices", DEVCG_SLICES)
+def test_mutants_cg_device(nslices):
+    """Every defect must be rejected by the checks the GPU tests run, at
+    every case.  ``alpha_rr``: alpha takes the (r,r) of the wrong iteration
+    (the one before; (b,b) in the first step) -- inside one iteration
+    rr_new does not exist yet when alpha is formed."""
+    case = _devcg(nslices)
+    from functools import partial
+
+    _devcg_check_all(partial(_emulate_device_cg, case, None), case)
+    for m in DEVCG_MUTANTS:
+        with pytest.raises(AssertionError):
+            _devcg_check_all(partial(_emulate_device_cg, case, m), case)
+        print(f"mutant {m}: rejected")

@@ -161,18 +161,45 @@ def next_multi_k(kg: int, widths=(2, 4, 8)) -> int:
     return next(kk for kk in widths if kk >= kg)
 
 
-def block_results(solver: str, ncols: int, active: list, conv_it: list,
-                  nit: int, breakdown: int, finish: list | None, bnrm: list,
-                  rr0: list, rr: list, met, maxits: int, res_atol: float,
-                  res_rtol: float, tsolve: float, flops_per_it: float) -> list:
+class ColumnTolerances:
+    """Per-column stopping test of one multi-RHS group, the same on the CPU
+    and the GPU: column c has met its tolerance when ``rr`` (a residual
+    norm SQUARED) is at most ``max(res_atol, res_rtol*bnrm[c])**2``; with a
+    zero tolerance only an exactly zero residual counts.  ``conv_it[c]`` is
+    the first iteration at which column c met it (None: not yet; 0: the
+    initial residual ``rr0[c]`` already did)."""
+
+    def __init__(self, bnrm: list, rr0: list, res_atol: float,
+                 res_rtol: float):
+        self.rtol2 = [max(res_atol, res_rtol * bn) ** 2 for bn in bnrm]
+        self.conv_it: list = [0 if self.met(c, rr) else None
+                              for c, rr in enumerate(rr0)]
+
+    def met(self, c: int, rr: float) -> bool:
+        return rr <= self.rtol2[c] if self.rtol2[c] > 0 else rr == 0.0
+
+    def record(self, c: int, rr: float, it: int) -> None:
+        if self.conv_it[c] is None and self.met(c, rr):
+            self.conv_it[c] = it
+
+    def all_met(self) -> bool:
+        return all(ci is not None for ci in self.conv_it)
+
+
+def block_results(solver: str, ncols: int, active: list,
+                  tol: ColumnTolerances, nit: int, breakdown: int,
+                  finish: list | None, bnrm: list, rr0: list, rr: list,
+                  maxits: int, res_atol: float, res_rtol: float,
+                  tsolve: float, flops_per_it: float) -> list:
     """SolveResults of one ``solve_block`` group, the same bookkeeping on
     the CPU and the GPU.  ``active`` lists the group columns that formed
-    the block (the others had a zero initial residual), ``conv_it[c]`` the
-    block iteration at which column c first met its tolerance (None: not
-    yet), ``nit`` the block iterations run, ``rr[c]`` the last recurrence
-    residual norm squared.  After a breakdown at block iteration
+    the block (the others had a zero initial residual), ``tol.conv_it[c]``
+    the block iteration at which column c first met its tolerance (None:
+    not yet), ``nit`` the block iterations run, ``rr[c]`` the last
+    recurrence residual norm squared.  After a breakdown at block iteration
     ``breakdown`` >= 0, ``finish[i]`` is the solve_multi result of
     ``active[i]``: its iterations are added to the block's."""
+    conv_it, met = tol.conv_it, tol.met
     out = []
     for c in range(ncols):
         res = SolveResult(solver=solver, maxits=maxits, res_atol=res_atol,

@@ -23,9 +23,9 @@ import torch
 from ..dist.halo import HaloExchange
 from ..ops import torch_ref as ops
 from ..part.subdomain import LocalSystem
-from .base import (SolveResult, block_results, cg_flops_per_iter,
-                   check_multi_shapes, next_multi_k, refine,
-                   solve_multi_by_column)
+from .base import (ColumnTolerances, SolveResult, block_results,
+                   cg_flops_per_iter, check_multi_shapes, next_multi_k,
+                   refine, solve_multi_by_column)
 
 
 class CGSolverCPU:
@@ -189,20 +189,15 @@ class CGSolverCPU:
         R0 = B - T0
         bnrm = [math.sqrt(float(torch.dot(B[:, c], B[:, c]))) for c in range(kg0)]
         rr0 = [float(torch.dot(R0[:, c], R0[:, c])) for c in range(kg0)]
-        rtol2 = [max(res_atol, res_rtol * bn) ** 2 for bn in bnrm]
         for c in range(kg0):
             if not math.isfinite(rr0[c]):
                 raise FloatingPointError(
                     f"block CG: initial rr={rr0[c]} in column {c}")
-
-        def met(c: int, rr: float) -> bool:
-            return rr <= rtol2[c] if rtol2[c] > 0 else rr == 0.0
-
-        conv_it: list = [0 if met(c, rr0[c]) else None for c in range(kg0)]
+        tol = ColumnTolerances(bnrm, rr0, res_atol, res_rtol)
         active = [c for c in range(kg0) if rr0[c] != 0.0]
         rr = list(rr0)
         nit, bd, finish = 0, -1, None
-        if not all(ci is not None for ci in conv_it):
+        if not tol.all_met():
             kg = len(active)
             K = next_multi_k(kg, ops.MULTI_K)
 
@@ -237,9 +232,8 @@ class CGSolverCPU:
                         raise FloatingPointError(
                             f"block CG diverged: rr={v} in column {c} at it {nit}")
                     rr[c] = v
-                    if conv_it[c] is None and met(c, v):
-                        conv_it[c] = nit
-                if all(ci is not None for ci in conv_it):
+                    tol.record(c, v, nit)
+                if tol.all_met():
                     break
             if bd >= 0:
                 Xf = Xi[:, :kg].contiguous()
@@ -250,8 +244,8 @@ class CGSolverCPU:
             for i, c in enumerate(active):
                 X[:, c] = Xi[:, i]
         return block_results(
-            "cg-block", kg0, active, conv_it, nit, bd, finish, bnrm, rr0, rr,
-            met, maxits, res_atol, res_rtol, time.perf_counter() - t0,
+            "cg-block", kg0, active, tol, nit, bd, finish, bnrm, rr0, rr,
+            maxits, res_atol, res_rtol, time.perf_counter() - t0,
             cg_flops_per_iter(self.local.nnzA + self.local.nnzO, n))
 
     # -- mixed precision: fp32-stored operator + fp64 refinement (beyond

@@ -25,6 +25,7 @@ from __future__ import annotations
 
 import math
 import os
+import sys
 import time
 
 import numpy as np
@@ -33,9 +34,51 @@ import torch
 from ..dist.halo import HaloExchange
 from ..ops import gpu_ops as ops
 from ..part.subdomain import LocalSystem
-from .base import (SolveResult, block_results, cg_flops_per_iter,
-                   check_multi_shapes, next_multi_k, refine,
-                   solve_multi_by_column)
+from .base import (ColumnTolerances, SolveResult, block_results,
+                   cg_flops_per_iter, check_multi_shapes, next_multi_k,
+                   refine, solve_multi_by_column)
+
+
+class LaggedReadback:
+    """Ring of ``lag + 1`` pinned host buffers (``width`` doubles each) and
+    events for the lagged host convergence test: iteration k pushes its
+    value into slot ``k % (lag + 1)`` and the host reads iteration
+    ``k - lag``, so the test runs for every iteration while the host stays
+    ``lag`` iterations ahead of the GPU instead of blocking on each
+    iteration's tail.  What index j means (residual after j or after j + 1
+    iterations) is the caller's business."""
+
+    def __init__(self, width: int, lag: int):
+        self.lag = lag
+        self._buf = [torch.zeros(width, dtype=torch.float64, pin_memory=True)
+                     for _ in range(lag + 1)]
+        self._ev = [torch.cuda.Event() for _ in range(lag + 1)]
+
+    def push(self, k: int, src: torch.Tensor, stream) -> None:
+        """Enqueue on ``stream`` the D2H copy of ``src`` into slot k and
+        record the slot's event behind it."""
+        j = k % (self.lag + 1)
+        if stream == torch.cuda.current_stream(stream.device):
+            # the usual case; skips the stream context's two set_stream
+            # calls in the host-bound small-system loop
+            self._buf[j].copy_(src, non_blocking=True)
+        else:
+            with torch.cuda.stream(stream):
+                self._buf[j].copy_(src, non_blocking=True)
+        self._ev[j].record(stream)
+
+    def event(self, k: int):
+        return self._ev[k % (self.lag + 1)]
+
+    def get(self, j: int) -> torch.Tensor:
+        """Wait for slot j's copy; returns the pinned buffer (valid until
+        iteration ``j + lag + 1`` is pushed)."""
+        self._ev[j % (self.lag + 1)].synchronize()
+        return self._buf[j % (self.lag + 1)]
+
+    def tail(self, nit: int) -> range:
+        """The iterations still unread after ``nit`` pushes."""
+        return range(max(nit - self.lag, 0), nit)
 
 
 class CGSolverHIP:
@@ -278,6 +321,81 @@ class CGSolverHIP:
         if self.comm is not None and self.comm.size > 1:
             self.comm.allreduce_(self.scal[slot:slot + count])
 
+    def _halo_fork(self, x: torch.Tensor, span=None) -> None:
+        """Start the halo exchange of ``x`` on comm_stream, ordered after
+        what the current stream has queued (the reference's preadytosend).
+        A profiler ``span`` is opened between the wait and the exchange, so
+        it times the exchange and not the wait for x."""
+        self._ev_p.record(torch.cuda.current_stream(self.device))
+        self.comm_stream.wait_event(self._ev_p)
+        if span is not None:
+            span.__enter__()
+        with torch.cuda.stream(self.comm_stream):
+            self.halo.begin(x)
+
+    def _halo_join(self) -> None:
+        """Finish the exchange; the current stream waits for the ghost tail
+        (the reference's preceived)."""
+        with torch.cuda.stream(self.comm_stream):
+            self.halo.end()
+            self._ev_recv.record(self.comm_stream)
+        torch.cuda.current_stream(self.device).wait_event(self._ev_recv)
+
+    def _dist_capture_ok(self, use_graph: bool, failed_key: str) -> bool:
+        """Whether the whole distributed iteration may be captured into a
+        graph: asked for, several ranks, profiler off, a backend that can
+        capture, no earlier failure on this solver.  ACG_DIST_GRAPH=0 is
+        the operational kill switch (eager iterations everywhere)."""
+        serial = self.comm is None or self.comm.size == 1
+        return bool(use_graph and not serial and not self.prof.enabled
+                    and getattr(self.comm, "can_capture", False)
+                    and os.environ.get("ACG_DIST_GRAPH", "1") != "0"
+                    and not self._graphs.get(failed_key, False))
+
+    def _capture_dist(self, body, failed_key: str, what: str = ""):
+        """Record ``body()`` into a new graph and return it.  Capture is
+        rank-local and records without executing, so no rank-sync is
+        involved; ANY failure (e.g. the gloo test backend cannot capture)
+        sets ``failed_key`` -- a permanent fall-back to eager iterations
+        for this solver -- and returns None.  Mixed replay/eager ranks
+        remain correct because replay issues the identical collective
+        sequence."""
+        try:
+            graph = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(graph):
+                body()
+            return graph
+        except Exception as e:
+            self._graphs[failed_key] = True
+            torch.cuda.synchronize(self.device)
+            if self.comm is None or self.comm.rank == 0:
+                print(f"[acg_amd] {what}distributed graph capture unavailable "
+                      f"({type(e).__name__}); eager iterations",
+                      file=sys.stderr)
+            return None
+
+    def _count_work(self, res: SolveResult, flops_per_it: float) -> None:
+        """Always-on counters of a finished solve (reference
+        cghip.h:109-118)."""
+        res.nflops = res.niterations * flops_per_it
+        res.halo_bytes_sent = self.halo.bytes_sent
+        res.halo_msgs_sent = self.halo.nmsgs_sent
+        self.niterations_total += res.niterations
+
+    def _annotate_profile(self, res: SolveResult) -> None:
+        if not self.prof.enabled:
+            return
+        from .profiling import annotate_op_stats
+
+        idxb = None
+        if self.matfree is not None:
+            idxb = -8.0  # matrix-free: no vals (8 B) and no cols read
+        elif self.bsell is not None:
+            idxb = 4.0 / (self.bsell[3] ** 2)
+        annotate_op_stats(res, self.local, self.prof.collect(),
+                          idx_bytes_per_nnz=idxb)
+        self.prof.reset()
+
     def _format_name(self) -> str:
         if self.matfree is not None:
             return "matrix-free"
@@ -319,15 +437,9 @@ class CGSolverHIP:
         L = self.local
         vals32 = self._lowprec_values() if lowprec else None
         have_halo = self.comm is not None and self.comm.size > 1
-        cur = torch.cuda.current_stream(self.device)
-        halo_span = None
         if have_halo:
-            self._ev_p.record(cur)
-            self.comm_stream.wait_event(self._ev_p)
             halo_span = self.prof.span("halo", self.comm_stream)
-            halo_span.__enter__()  # closed after halo.end() below
-            with torch.cuda.stream(self.comm_stream):
-                self.halo.begin(xfull)
+            self._halo_fork(xfull, halo_span)  # closed after the join below
         fuse = dict(partials=self.partials,
                     scal=self.scal if fuse_dotslot >= 0 else None,
                     dotslot=fuse_dotslot)
@@ -370,12 +482,8 @@ class CGSolverHIP:
                          lanes=self.lanesA, accum=False, dot_accum=False,
                          **fuse)
         if have_halo:
-            with torch.cuda.stream(self.comm_stream):
-                self.halo.end()
-                self._ev_recv.record(self.comm_stream)
-            if halo_span is not None:
-                halo_span.__exit__(None, None, None)
-            cur.wait_event(self._ev_recv)
+            self._halo_join()
+            halo_span.__exit__(None, None, None)
         if L.nborder > 0 and self.local.nnzO > 0:
             with self.prof.span("spmvO"):
                 if self.matfree is not None:
@@ -509,22 +617,16 @@ class CGSolverHIP:
         # multi-GPU: capture the whole distributed iteration (see docstring)
         dist_key = gkey + ":dist"
         dist_failed_key = "classic:capture_failed"
-        dist_graph_ok = (use_graph and not serial and not self.prof.enabled
-                         and not fold
-                         and getattr(self.comm, "can_capture", False)
-                         and os.environ.get("ACG_DIST_GRAPH", "1") != "0"
-                         and not self._graphs.get(dist_failed_key, False))
+        dist_graph_ok = (not fold
+                         and self._dist_capture_ok(use_graph, dist_failed_key))
         dgraph = self._graphs.get(dist_key) if dist_graph_ok else None
         # lag-2 convergence pipeline (+ optional hipGraph replay), mirroring
         # solve_pipelined (the host test runs for every iteration; the host
         # reads the value two iterations late).  Classic's rr copy lands at
-        # the END of its iteration, so LAG=1 would make the host wake
-        # exactly when the GPU drains -- LAG=2 keeps one full iteration
+        # the END of its iteration, so lag 1 would make the host wake
+        # exactly when the GPU drains -- lag 2 keeps one full iteration
         # queued and the GPU never idles (measured 582 -> ~545 us/it).
-        LAG = 2
-        hostbuf = [torch.zeros(1, dtype=torch.float64, pin_memory=True)
-                   for _ in range(LAG + 1)]
-        evdone = [torch.cuda.Event() for _ in range(LAG + 1)]
+        ring = LaggedReadback(1, lag=2)
 
         def body(k: int = 0):
             if fold:
@@ -552,13 +654,10 @@ class CGSolverHIP:
             with self.prof.span("daypx"):
                 S.daypx_ratio(p, r, scal, S.S_RR, S.S_RR_PREV, n=n)
 
-        def read_rr(j):
-            evdone[j % (LAG + 1)].synchronize()
-            return float(hostbuf[j % (LAG + 1)][0])
-
         def check(j):
+            """Host test of rr after iteration j."""
             nonlocal rr, converged
-            rr = read_rr(j)
+            rr = float(ring.get(j)[0])
             if not math.isfinite(rr):
                 raise FloatingPointError(f"CG diverged: rr={rr} at it {j + 1}")
             if rtol2 > 0 and rr <= rtol2:
@@ -569,8 +668,9 @@ class CGSolverHIP:
 
         k = 0
         cur = torch.cuda.current_stream(self.device)
+        rr_slot = scal[S.S_RR:S.S_RR + 1]
         while k < maxits:
-            if k >= LAG and check(k - LAG):
+            if k >= ring.lag and check(k - ring.lag):
                 break
             if graph is not None:
                 graph.replay()
@@ -584,34 +684,21 @@ class CGSolverHIP:
                         body()
                     self._graphs[gkey] = graph
                 elif dist_graph_ok and k == 2 and dgraph is None:
-                    # RCCL channels are warm after 2 eager iterations;
-                    # capture records without executing (rank-local)
-                    try:
-                        gg = torch.cuda.CUDAGraph()
-                        with torch.cuda.graph(gg):
-                            body()
-                        dgraph = gg
-                        self._graphs[dist_key] = gg
-                    except Exception as e:
-                        self._graphs[dist_failed_key] = True
-                        torch.cuda.synchronize(self.device)
-                        if self.comm is None or self.comm.rank == 0:
-                            print(f"[acg_amd] classic distributed graph "
-                                  f"capture unavailable ({type(e).__name__});"
-                                  f" eager iterations",
-                                  file=__import__("sys").stderr)
+                    # RCCL channels are warm after 2 eager iterations
+                    dgraph = self._capture_dist(body, dist_failed_key,
+                                                "classic ")
+                    if dgraph is not None:
+                        self._graphs[dist_key] = dgraph
             # lagged rr D2H on the SAME stream: cross-stream event chains
             # measured ~20 us each in fire->launch latency (45 us/iter of
             # the iteration period); the in-order 8-byte copy costs ~3 us
             # on the critical path and makes the overwrite race impossible
             # by stream ordering.
-            j = k % (LAG + 1)
-            hostbuf[j].copy_(scal[S.S_RR:S.S_RR + 1], non_blocking=True)
-            evdone[j].record(cur)
+            ring.push(k, rr_slot, cur)
             k += 1
             res.niterations = k
         if not converged:
-            for j in range(max(maxits - LAG, 0), maxits):
+            for j in ring.tail(maxits):
                 if check(j):
                     break
         return self._finish_classic(res, x, xi, converged, rtol2, t0)
@@ -660,21 +747,8 @@ class CGSolverHIP:
         res.rnrm2 = math.sqrt(max(rr, 0.0))
         res.converged = converged or (rtol2 > 0 and rr <= rtol2)
         nnz_full = self.local.nnzA + self.local.nnzO
-        res.nflops = res.niterations * cg_flops_per_iter(nnz_full, self.n)
-        res.halo_bytes_sent = self.halo.bytes_sent
-        res.halo_msgs_sent = self.halo.nmsgs_sent
-        self.niterations_total += res.niterations
-        if self.prof.enabled:
-            from .profiling import annotate_op_stats
-
-            idxb = None
-            if self.matfree is not None:
-                idxb = -8.0  # matrix-free: no vals (8 B) and no cols read
-            elif self.bsell is not None:
-                idxb = 4.0 / (self.bsell[3] ** 2)
-            annotate_op_stats(res, self.local, self.prof.collect(),
-                              idx_bytes_per_nnz=idxb)
-            self.prof.reset()
+        self._count_work(res, cg_flops_per_iter(nnz_full, self.n))
+        self._annotate_profile(res)
         return res
 
     # -- multiple right-hand sides (beyond reference) ----------------------
@@ -746,71 +820,96 @@ class CGSolverHIP:
             ops.spmm_sell(sellptr, scols, svals, self.n, Xm, Y,
                           perm=self.sell_perm, **fuse)
 
+    def _multi_ws(self, kind: str, K: int) -> dict:
+        """Persistent (rows, K) buffers of one group width, kept as
+        ``_ws["multi{K}"]`` (residual R, direction P) or ``_ws["block{K}"]``
+        (Q, S, the coefficient state and two more rr_out slots for the
+        breakdown flag and its iteration)."""
+        key = f"{kind}{K}"
+        ws = self._ws.get(key)
+        if ws is None:
+            block = kind == "block"
+            resid, dirn = ("Q", "S") if block else ("R", "P")
+
+            def mv(rows):
+                return torch.zeros(rows, K, dtype=torch.float64,
+                                   device=self.device)
+            ws = self._ws[key] = {
+                resid: mv(self.n), "T": mv(self.n), "Bp": mv(self.n),
+                dirn: mv(self.nlocal), "Xi": mv(self.nlocal),
+                "scal": ops.alloc_scalars_multi(self.device, K),
+                "partials": ops.alloc_partials_multi(self.device, K),
+            }
+            if block:
+                ws["state"] = ops.alloc_block_state(self.device)
+            ws["rr_out"] = torch.zeros(K + 2 if block else K,
+                                       dtype=torch.float64, device=self.device)
+        return ws
+
+    def _multi_prologue(self, ws: dict, B, X, R, time_padding: bool):
+        """Start of a multi-RHS group: B and X zero-padded to the workspace
+        width, ``R = Bp - A Xi`` and the norms of the real columns.
+        Returns (t0, bnrm, rr0), rr0 squared.  The timing window opens
+        before the padding copies or after them, as the caller has always
+        reported its ``tsolve``."""
+        S = ops
+        n, kg = self.n, B.shape[1]
+        Bp, Xi, T = ws["Bp"], ws["Xi"], ws["T"]
+        scal, partials = ws["scal"], ws["partials"]
+
+        def start() -> float:
+            torch.cuda.synchronize(self.device)
+            return time.perf_counter()
+
+        if time_padding:
+            t0 = start()
+        scal.zero_()
+        Bp.zero_()
+        Bp[:, :kg] = B
+        Xi.zero_()
+        Xi[:, :kg] = X
+        if not time_padding:
+            t0 = start()
+        S.dot_multi(Bp, Bp, partials, scal, S.S_BNRM2, n=n)
+        self._spmm(Xi, T, scal, partials)
+        torch.sub(Bp, T, out=R)
+        S.dot_multi(R, R, partials, scal, S.S_RR, n=n)
+        slab = scal.cpu()
+        bnrm = [math.sqrt(max(float(slab[c, S.S_BNRM2]), 0.0)) for c in range(kg)]
+        rr0 = [float(slab[c, S.S_RR]) for c in range(kg)]
+        return t0, bnrm, rr0
+
     def _solve_multi_group(self, B, X, K: int, maxits: int, res_atol: float,
                            res_rtol: float) -> list:
         """One group of kg <= K columns on the SpMM iteration (eager, same
         lag-2 host test as _solve_classic, reading the contiguous rr_out)."""
         S = ops
         n, kg = self.n, B.shape[1]
-        key = f"multi{K}"
-        ws = self._ws.get(key)
-        if ws is None:
-            def mv(rows):
-                return torch.zeros(rows, K, dtype=torch.float64,
-                                   device=self.device)
-            ws = self._ws[key] = {
-                "R": mv(n), "T": mv(n), "Bp": mv(n), "P": mv(self.nlocal),
-                "Xi": mv(self.nlocal),
-                "scal": S.alloc_scalars_multi(self.device, K),
-                "partials": S.alloc_partials_multi(self.device, K),
-                "rr_out": torch.zeros(K, dtype=torch.float64, device=self.device),
-            }
-        R, T, Bp, P, Xi = ws["R"], ws["T"], ws["Bp"], ws["P"], ws["Xi"]
+        ws = self._multi_ws("multi", K)
+        R, T, P, Xi = ws["R"], ws["T"], ws["P"], ws["Xi"]
         scal, partials, rr_out = ws["scal"], ws["partials"], ws["rr_out"]
-        scal.zero_()
-        Bp.zero_()
-        Bp[:, :kg] = B
-        Xi.zero_()
-        Xi[:, :kg] = X
         P.zero_()
-        torch.cuda.synchronize(self.device)
-        t0 = time.perf_counter()
-        S.dot_multi(Bp, Bp, partials, scal, S.S_BNRM2, n=n)
-        self._spmm(Xi, T, scal, partials)
-        torch.sub(Bp, T, out=R)
+        t0, bnrm, rr0 = self._multi_prologue(ws, B, X, R, time_padding=False)
         P[:n] = R
-        S.dot_multi(R, R, partials, scal, S.S_RR, n=n)
-        slab = scal.cpu()
-        bnrm = [math.sqrt(max(float(slab[c, S.S_BNRM2]), 0.0)) for c in range(kg)]
-        rr0 = [float(slab[c, S.S_RR]) for c in range(kg)]
-        rtol2 = [max(res_atol, res_rtol * bn) ** 2 for bn in bnrm]
-
-        def met(c: int, rr: float) -> bool:
-            return rr <= rtol2[c] if rtol2[c] > 0 else rr == 0.0
-
-        conv_it: list = [0 if met(c, rr0[c]) else None for c in range(kg)]
-        LAG = 2
-        hostbuf = [torch.zeros(K, dtype=torch.float64, pin_memory=True)
-                   for _ in range(LAG + 1)]
-        evdone = [torch.cuda.Event() for _ in range(LAG + 1)]
+        tol = ColumnTolerances(bnrm, rr0, res_atol, res_rtol)
+        ring = LaggedReadback(K, lag=2)
 
         def check(j: int) -> bool:
-            evdone[j % (LAG + 1)].synchronize()
-            rrs = hostbuf[j % (LAG + 1)]
+            """Host test of rr_out after iteration j."""
+            rrs = ring.get(j)
             for c in range(kg):
                 rr = float(rrs[c])
                 if not math.isfinite(rr):
                     raise FloatingPointError(
                         f"CG diverged: rr={rr} in column {c} at it {j + 1}")
-                if conv_it[c] is None and met(c, rr):
-                    conv_it[c] = j + 1
-            return all(ci is not None for ci in conv_it)
+                tol.record(c, rr, j + 1)
+            return tol.all_met()
 
         nit = 0
-        done = all(ci is not None for ci in conv_it)
+        done = tol.all_met()
         cur = torch.cuda.current_stream(self.device)
         while not done and nit < maxits:
-            if nit >= LAG and check(nit - LAG):
+            if nit >= ring.lag and check(nit - ring.lag):
                 done = True
                 break
             with self.prof.span("spmvA"):
@@ -820,12 +919,10 @@ class CGSolverHIP:
                 S.cg_finalize_multi(partials, nb, scal, rr_out)
             with self.prof.span("daypx"):
                 S.daypx_ratio_multi(P, R, scal, n=n)
-            j = nit % (LAG + 1)
-            hostbuf[j].copy_(rr_out, non_blocking=True)
-            evdone[j].record(cur)
+            ring.push(nit, rr_out, cur)
             nit += 1
         if not done:
-            for j in range(max(nit - LAG, 0), nit):
+            for j in ring.tail(nit):
                 if check(j):
                     break
         torch.cuda.synchronize(self.device)
@@ -843,8 +940,8 @@ class CGSolverHIP:
             res.bnrm2 = bnrm[c]
             res.r0nrm2 = math.sqrt(max(rr0[c], 0.0))
             res.rnrm2 = math.sqrt(max(rr, 0.0))
-            res.converged = conv_it[c] is not None or met(c, rr)
-            res.niterations = conv_it[c] if conv_it[c] is not None else nit
+            res.converged = tol.conv_it[c] is not None or tol.met(c, rr)
+            res.niterations = tol.conv_it[c] if tol.conv_it[c] is not None else nit
             res.tsolve = tsolve
             res.nflops = res.niterations * cg_flops_per_iter(nnz_full, n)
             out.append(res)
@@ -881,24 +978,6 @@ class CGSolverHIP:
                                            maxits, res_atol, res_rtol)
         return out
 
-    def _block_ws(self, K: int) -> dict:
-        key = f"block{K}"
-        ws = self._ws.get(key)
-        if ws is None:
-            def mv(rows):
-                return torch.zeros(rows, K, dtype=torch.float64,
-                                   device=self.device)
-            ws = self._ws[key] = {
-                "Q": mv(self.n), "T": mv(self.n), "Bp": mv(self.n),
-                "S": mv(self.nlocal), "Xi": mv(self.nlocal),
-                "scal": ops.alloc_scalars_multi(self.device, K),
-                "partials": ops.alloc_partials_multi(self.device, K),
-                "state": ops.alloc_block_state(self.device),
-                "rr_out": torch.zeros(K + 2, dtype=torch.float64,
-                                      device=self.device),
-            }
-        return ws
-
     def _solve_block_group(self, B, X, maxits: int, res_atol: float,
                            res_rtol: float) -> list:
         """One group of up to multi_group columns (eager; the lag-2 host
@@ -906,50 +985,29 @@ class CGSolverHIP:
         iteration from one (K + 2)-double copy)."""
         S = ops
         n, kg0 = self.n, B.shape[1]
-        ws = self._block_ws(next_multi_k(kg0, S.MULTI_K))
-        torch.cuda.synchronize(self.device)
-        t0 = time.perf_counter()
+        ws = self._multi_ws("block", next_multi_k(kg0, S.MULTI_K))
+        Xi, Q = ws["Xi"], ws["Q"]
         # R0 = B - A X0 and the norms of the whole group
-        Bp, Xi, Q, T = ws["Bp"], ws["Xi"], ws["Q"], ws["T"]
-        scal, partials = ws["scal"], ws["partials"]
-        scal.zero_()
-        Bp.zero_()
-        Bp[:, :kg0] = B
-        Xi.zero_()
-        Xi[:, :kg0] = X
-        S.dot_multi(Bp, Bp, partials, scal, S.S_BNRM2, n=n)
-        self._spmm(Xi, T, scal, partials)
-        torch.sub(Bp, T, out=Q)
-        S.dot_multi(Q, Q, partials, scal, S.S_RR, n=n)
-        slab = scal.cpu()
-        bnrm = [math.sqrt(max(float(slab[c, S.S_BNRM2]), 0.0)) for c in range(kg0)]
-        rr0 = [float(slab[c, S.S_RR]) for c in range(kg0)]
-        rtol2 = [max(res_atol, res_rtol * bn) ** 2 for bn in bnrm]
+        t0, bnrm, rr0 = self._multi_prologue(ws, B, X, Q, time_padding=True)
         for c in range(kg0):
             if not math.isfinite(rr0[c]):
                 raise FloatingPointError(
                     f"block CG: initial rr={rr0[c]} in column {c}")
-
-        def met(c: int, rr: float) -> bool:
-            return rr <= rtol2[c] if rtol2[c] > 0 else rr == 0.0
-
-        conv_it: list = [0 if met(c, rr0[c]) else None for c in range(kg0)]
+        tol = ColumnTolerances(bnrm, rr0, res_atol, res_rtol)
         active = [c for c in range(kg0) if rr0[c] != 0.0]
         rr = list(rr0)
         nit, bd, finish = 0, -1, None
-        if not all(ci is not None for ci in conv_it):
+        if not tol.all_met():
             kg = len(active)
             K = next_multi_k(kg, S.MULTI_K)
             Ract, Xact = Q[:, active], Xi[:, active]  # copies
-            ws = self._block_ws(K)
-            Xi, Q, T, Sm = ws["Xi"], ws["Q"], ws["T"], ws["S"]
-            partials, state, rr_out = ws["partials"], ws["state"], ws["rr_out"]
-            for buf in (Xi, Q, Sm, state, rr_out):
+            ws = self._multi_ws("block", K)
+            Xi, Q = ws["Xi"], ws["Q"]
+            for buf in (Xi, Q, ws["S"], ws["state"], ws["rr_out"]):
                 buf.zero_()
             Xi[:, :kg] = Xact
             Q[:, :kg] = Ract
-            nit, bd = self._block_iterate(ws, K, kg, active, conv_it, rr, met,
-                                          maxits)
+            nit, bd = self._block_iterate(ws, K, kg, active, tol, rr, maxits)
             if bd >= 0:
                 Xf = Xi[:, :kg].contiguous()
                 finish = self.solve_multi(B[:, active].contiguous(), Xf,
@@ -964,30 +1022,28 @@ class CGSolverHIP:
             self.prof.reset()
         self.niterations_total += nit
         return block_results(
-            "cg-hip-block", kg0, active, conv_it, nit, bd, finish, bnrm, rr0,
-            rr, met, maxits, res_atol, res_rtol, tsolve,
+            "cg-hip-block", kg0, active, tol, nit, bd, finish, bnrm, rr0, rr,
+            maxits, res_atol, res_rtol, tsolve,
             cg_flops_per_iter(self.local.nnzA + self.local.nnzO, n))
 
     def _block_iterate(self, ws: dict, K: int, kg: int, active: list,
-                       conv_it: list, rr: list, met, maxits: int):
+                       tol: ColumnTolerances, rr: list, maxits: int):
         """The block iteration on a prepared workspace (Q = R0, S = 0,
-        state = 0).  Updates conv_it / rr of the active columns; returns
+        state = 0).  Updates tol / rr of the active columns; returns
         (block iterations run, breakdown iteration or -1)."""
         S = ops
         n = self.n
         Xi, Q, T, Sm = ws["Xi"], ws["Q"], ws["T"], ws["S"]
         partials, state, rr_out = ws["partials"], ws["state"], ws["rr_out"]
-        LAG = 2
-        hostbuf = [torch.zeros(K + 2, dtype=torch.float64, pin_memory=True)
-                   for _ in range(LAG + 1)]
-        evdone = [torch.cuda.Event() for _ in range(LAG + 1)]
+        ring = LaggedReadback(K + 2, lag=2)
         cur = torch.cuda.current_stream(self.device)
         bd = -1
 
-        def read(buf, it: int) -> bool:
-            """Host test of the state after block iteration ``it``; True
+        def check(j: int) -> bool:
+            """Host test of the state after block iteration ``j + 1``; True
             when the group is finished (all met, or breakdown)."""
             nonlocal bd
+            buf, it = ring.get(j), j + 1
             if float(buf[K]) != 0.0:
                 bd = int(buf[K + 1])
                 return True
@@ -997,9 +1053,8 @@ class CGSolverHIP:
                     raise FloatingPointError(
                         f"block CG diverged: rr={v} in column {c} at it {it}")
                 rr[c] = v
-                if conv_it[c] is None and met(c, v):
-                    conv_it[c] = it
-            return all(ci is not None for ci in conv_it)
+                tol.record(c, v, it)
+            return tol.all_met()
 
         # start-up: Q <- R0 zeta^-1, C = zeta, S = Q
         with self.prof.span("block_init"):
@@ -1009,14 +1064,10 @@ class CGSolverHIP:
         if float(rr_out.cpu()[K]) != 0.0:
             return 0, 0
 
-        def check(j: int) -> bool:
-            evdone[j % (LAG + 1)].synchronize()
-            return read(hostbuf[j % (LAG + 1)], j + 1)
-
         nit = 0
         done = False
         while not done and nit < maxits:
-            if nit >= LAG and check(nit - LAG):
+            if nit >= ring.lag and check(nit - ring.lag):
                 done = True
                 break
             with self.prof.span("spmvA"):
@@ -1029,12 +1080,10 @@ class CGSolverHIP:
                 S.block_coef_beta(partials, nb, state, rr_out, K, kg, nit + 1)
             with self.prof.span("block_ortho"):
                 S.block_ortho(Q, Sm, state, n)
-            j = nit % (LAG + 1)
-            hostbuf[j].copy_(rr_out, non_blocking=True)
-            evdone[j].record(cur)
+            ring.push(nit, rr_out, cur)
             nit += 1
         if not done:
-            for j in range(max(nit - LAG, 0), nit):
+            for j in ring.tail(nit):
                 if check(j):
                     break
         torch.cuda.synchronize(self.device)
@@ -1161,8 +1210,8 @@ class CGSolverHIP:
                 f"CG diverged: rr={rr} at it {res.niterations}")
         res.converged = bool(conv)
         nnz_full = self.local.nnzA + self.local.nnzO
-        res.nflops = res.niterations * cg_flops_per_iter(nnz_full, n)
-        self.niterations_total += res.niterations
+        # (one rank never exchanges a halo: its counters stay zero)
+        self._count_work(res, cg_flops_per_iter(nnz_full, n))
         return res
 
     # -- Jacobi-preconditioned CG (beyond reference: aCG is strictly
@@ -1253,10 +1302,7 @@ class CGSolverHIP:
         res.rnrm2 = math.sqrt(max(rr, 0.0))
         res.converged = converged
         nnz_full = L.nnzA + L.nnzO
-        res.nflops = res.niterations * (cg_flops_per_iter(nnz_full, n) + 3.0 * n)
-        res.halo_bytes_sent = self.halo.bytes_sent
-        res.halo_msgs_sent = self.halo.nmsgs_sent
-        self.niterations_total += res.niterations
+        self._count_work(res, cg_flops_per_iter(nnz_full, n) + 3.0 * n)
         return res
 
     # -- pipelined CG -----------------------------------------------------
@@ -1342,12 +1388,8 @@ class CGSolverHIP:
             """One megafused iteration: halo(wa) || matA pass (SpMV + update
             of interior rows), then matO pass finishing border rows."""
             have_halo = not serial
-            cur = torch.cuda.current_stream(self.device)
             if have_halo:
-                self._ev_p.record(cur)
-                self.comm_stream.wait_event(self._ev_p)
-                with torch.cuda.stream(self.comm_stream):
-                    self.halo.begin(wa)
+                self._halo_fork(wa)
             border_base = L.ninterior if L.nnzO > 0 else n
             if self.matfree is not None:
                 nbA = S.stencil_pipe(self.matfree, n, 0, border_base, wa,
@@ -1360,10 +1402,7 @@ class CGSolverHIP:
                                   self.partials, 0, mato=False)
             nb = nbA
             if have_halo:
-                with torch.cuda.stream(self.comm_stream):
-                    self.halo.end()
-                    self._ev_recv.record(self.comm_stream)
-                cur.wait_event(self._ev_recv)
+                self._halo_join()
             if L.nnzO > 0:
                 if self.matfree is not None:
                     nbO = S.stencil_pipe(self.matfree, L.nborder, L.ninterior,
@@ -1386,28 +1425,12 @@ class CGSolverHIP:
         # host<->GPU and costs ~8% at Queen scale).  On the detecting
         # iteration 1-2 extra (valid) updates have been applied to x;
         # reported niterations/rnrm2 correspond to the detected gamma.
-        LAG = 1
-        hostbuf = [torch.zeros(1, dtype=torch.float64, pin_memory=True)
-                   for _ in range(LAG + 1)]
-        evdone = [torch.cuda.Event() for _ in range(LAG + 1)]
-
-        def issue_gamma_copy(k):
-            # same-stream D2H (cross-stream event chains cost ~20 us each
-            # in fire->launch latency; the in-order 8-byte copy ~3 us) --
-            # also makes the gamma-overwrite race impossible by ordering
-            cur = torch.cuda.current_stream(self.device)
-            j = k % (LAG + 1)
-            hostbuf[j].copy_(scal[S.S_GAMMA:S.S_GAMMA + 1], non_blocking=True)
-            evdone[j].record(cur)
-
-        def read_gamma(j):
-            evdone[j % (LAG + 1)].synchronize()
-            return float(hostbuf[j % (LAG + 1)][0])
+        ring = LaggedReadback(1, lag=1)
 
         def check(j):
             """Host convergence test on gamma_j; True => converged at j."""
             nonlocal gamma_host, converged
-            gamma_host = read_gamma(j)
+            gamma_host = float(ring.get(j)[0])
             if j == 0:
                 res.r0nrm2 = math.sqrt(max(gamma_host, 0.0))
             if not math.isfinite(gamma_host):
@@ -1428,20 +1451,11 @@ class CGSolverHIP:
         # side-stream allreduce fork, halo send/recv, split SpMV, fused
         # update + finalize -- is captured once and replayed (RCCL
         # collectives and event forks are capturable; the 8-byte gamma
-        # D2H stays outside, same-stream after the replay).  Capture is
-        # rank-local and records without executing, so no rank-sync is
-        # involved; ANY capture failure (e.g. the gloo test backend
-        # cannot capture) permanently falls back to the eager path for
-        # this solver, and mixed replay/eager ranks remain correct
-        # because replay issues the identical collective sequence.
+        # D2H stays outside, same-stream after the replay).  A capture
+        # failure falls back to the eager path for good (_capture_dist).
         dist_key = wskey + ":dist"  # dist bodies INCLUDE the allreduce --
         dist_failed_key = wskey + ":capture_failed"  # never mix with serial
-        # ACG_DIST_GRAPH=0 is the operational kill switch for the captured
-        # distributed iteration (falls back to the eager path everywhere)
-        dist_graph_ok = (use_graph and not serial and not self.prof.enabled
-                         and getattr(self.comm, "can_capture", False)
-                         and os.environ.get("ACG_DIST_GRAPH", "1") != "0"
-                         and not self._graphs.get(dist_failed_key, False))
+        dist_graph_ok = self._dist_capture_ok(use_graph, dist_failed_key)
         dgraph = self._graphs.get(dist_key) if dist_graph_ok and not mega else None
         dgraphs = (self._graphs.get(dist_key, [None, None])
                    if dist_graph_ok and mega else [None, None])
@@ -1455,71 +1469,50 @@ class CGSolverHIP:
             ws["gsnap"] = torch.zeros(1, dtype=torch.float64,
                                       device=self.device)
         gsnap = ws["gsnap"]
+        gamma = scal[S.S_GAMMA:S.S_GAMMA + 1]
+
+        def fork_allreduce():
+            """The 2-double (gamma, delta) allreduce on allred_stream,
+            ordered after what the current stream has queued; ev_ar marks
+            its end."""
+            ev_gd.record(torch.cuda.current_stream(self.device))
+            self.allred_stream.wait_event(ev_gd)
+            with torch.cuda.stream(self.allred_stream):
+                with self.prof.span("allreduce", self.allred_stream):
+                    self._allreduce_slot(S.S_GAMMA, 2)
+                ev_ar.record(self.allred_stream)
 
         def body_dist(wa=None, wb=None):
             """One steady-state (first=False) distributed iteration in the
             shape the capture needs (allreduce included)."""
             if mega:
                 self._allreduce_slot(S.S_GAMMA, 2)
-                gsnap.copy_(scal[S.S_GAMMA:S.S_GAMMA + 1])
+                gsnap.copy_(gamma)
                 mega_body(wa, wb, False)
             else:
-                cur = torch.cuda.current_stream(self.device)
-                ev_gd.record(cur)
-                self.allred_stream.wait_event(ev_gd)
-                with torch.cuda.stream(self.allred_stream):
-                    self._allreduce_slot(S.S_GAMMA, 2)
-                    ev_ar.record(self.allred_stream)
+                fork_allreduce()
                 self._spmv_overlapped(w, q)
-                cur.wait_event(ev_ar)
-                gsnap.copy_(scal[S.S_GAMMA:S.S_GAMMA + 1])
+                torch.cuda.current_stream(self.device).wait_event(ev_ar)
+                gsnap.copy_(gamma)
                 S.pipelined_fused(z, t, p, xi, r, w, q, scal, self.partials,
                                   n, False)
 
-        def try_capture_dist(kk):
-            nonlocal dgraph
-            if self._graphs.get(dist_failed_key):
-                return
-            try:
-                gg = torch.cuda.CUDAGraph()
-                if mega:
-                    wa, wb = (w, w2) if kk % 2 == 0 else (w2, w)
-                    with torch.cuda.graph(gg):
-                        body_dist(wa, wb)
-                    dgraphs[kk % 2] = gg
-                    self._graphs[dist_key] = dgraphs
-                else:
-                    with torch.cuda.graph(gg):
-                        body_dist()
-                    dgraph = gg
-                    self._graphs[dist_key] = gg
-            except Exception as e:
-                self._graphs[dist_failed_key] = True
-                torch.cuda.synchronize(self.device)
-                if (self.comm is None or self.comm.rank == 0):
-                    print(f"[acg_amd] distributed graph capture unavailable "
-                          f"({type(e).__name__}); eager iterations",
-                          file=__import__("sys").stderr)
-
         k = 0
+        cur = torch.cuda.current_stream(self.device)
         while k < maxits:
             first = (k == 0)
-            if not serial and dist_graph_ok:
-                g = dgraphs[k % 2] if mega else dgraph
-                if g is not None and k > 0:
-                    # whole iteration (incl. allreduce) is in the graph
-                    if k >= LAG and check(k - LAG):
-                        break
-                    g.replay()
-                    # same slot/value as the eager path: the ALLREDUCED
-                    # previous gamma, snapshotted inside the replay
-                    cur = torch.cuda.current_stream(self.device)
-                    j = k % (LAG + 1)
-                    hostbuf[j].copy_(gsnap, non_blocking=True)
-                    evdone[j].record(cur)
-                    k += 1
-                    res.niterations = k
-                    continue
+            g = dgraphs[k % 2] if mega else dgraph
+            if g is not None and k > 0:
+                # whole iteration (incl. allreduce) is in the graph
+                if k >= ring.lag and check(k - ring.lag):
+                    break
+                g.replay()
+                # same slot/value as the eager path: the ALLREDUCED
+                # previous gamma, snapshotted inside the replay
+                ring.push(k, gsnap, cur)
+                k += 1
+                res.niterations = k
+                continue
             # ONE 2-double allreduce per iteration (gamma,delta adjacent).
             # Multi-GPU non-megafused: the allreduce rides a dedicated side
             # stream so SpMV(q = A w) -- which does not read the scalars --
@@ -1527,32 +1520,26 @@ class CGSolverHIP:
             # of Ghysels-Vanroose pipelining: reference cghip.c:1750-1811).
             overlap_ar = (not serial) and not mega
             if overlap_ar:
-                cur = torch.cuda.current_stream(self.device)
-                ev_gd.record(cur)
-                self.allred_stream.wait_event(ev_gd)
-                with torch.cuda.stream(self.allred_stream):
-                    with self.prof.span("allreduce", self.allred_stream):
-                        self._allreduce_slot(S.S_GAMMA, 2)
-                    ev_ar.record(self.allred_stream)
+                fork_allreduce()
             else:
                 with self.prof.span("allreduce"):
                     self._allreduce_slot(S.S_GAMMA, 2)
             # lagged host test of the previous iteration's gamma (read
-            # BEFORE issuing this iteration's copy: LAG+1 buffers rotate)
-            if k >= LAG and check(k - LAG):
+            # BEFORE issuing this iteration's copy: lag+1 buffers rotate)
+            if k >= ring.lag and check(k - ring.lag):
                 break
             if overlap_ar:
                 # D2H of gamma chains off the allreduce, not the main stream
                 # (the SpMV below must NOT wait for it -- that is the
                 # overlap; only the fused update is ordered after it)
-                j = k % (LAG + 1)
                 self.copy_stream.wait_event(ev_ar)
-                with torch.cuda.stream(self.copy_stream):
-                    hostbuf[j].copy_(scal[S.S_GAMMA:S.S_GAMMA + 1],
-                                     non_blocking=True)
-                    evdone[j].record(self.copy_stream)
+                ring.push(k, gamma, self.copy_stream)
             else:
-                issue_gamma_copy(k)  # same-stream: ordered by construction
+                # same-stream D2H (cross-stream event chains cost ~20 us
+                # each in fire->launch latency; the in-order 8-byte copy
+                # ~3 us) -- also makes the gamma-overwrite race impossible
+                # by ordering
+                ring.push(k, gamma, cur)
             if mega:
                 wa, wb = (w, w2) if k % 2 == 0 else (w2, w)
                 g = graphs[k % 2]
@@ -1574,9 +1561,8 @@ class CGSolverHIP:
                     # the fused update reads gamma/delta (allreduce) and its
                     # finalize overwrites them (in-flight D2H copy): order
                     # after both
-                    cur2 = torch.cuda.current_stream(self.device)
-                    cur2.wait_event(ev_ar)
-                    cur2.wait_event(evdone[k % (LAG + 1)])
+                    cur.wait_event(ev_ar)
+                    cur.wait_event(ring.event(k))
                 with self.prof.span("update"):
                     S.pipelined_fused(z, t, p, xi, r, w, q, scal, self.partials,
                                       n, first)
@@ -1588,15 +1574,21 @@ class CGSolverHIP:
                         S.pipelined_fused(z, t, p, xi, r, w, q, scal,
                                           self.partials, n, False)
                     self._graphs[wskey] = graph
-            if dist_graph_ok and not serial and (
-                    (mega and k in (2, 3) and dgraphs[k % 2] is None)
-                    or (not mega and k == 2 and dgraph is None)):
-                try_capture_dist(k)
+            if dist_graph_ok and not self._graphs.get(dist_failed_key):
+                if mega and k in (2, 3) and dgraphs[k % 2] is None:
+                    dgraphs[k % 2] = self._capture_dist(
+                        lambda: body_dist(wa, wb), dist_failed_key)
+                    if dgraphs[k % 2] is not None:
+                        self._graphs[dist_key] = dgraphs
+                elif not mega and k == 2 and dgraph is None:
+                    dgraph = self._capture_dist(body_dist, dist_failed_key)
+                    if dgraph is not None:
+                        self._graphs[dist_key] = dgraph
             k += 1
             res.niterations = k
         if not converged:
             # drain the lagged checks for the tail iterations
-            for j in range(max(maxits - LAG, 0), maxits):
+            for j in ring.tail(maxits):
                 if check(j):
                     break
         torch.cuda.synchronize(self.device)
@@ -1606,19 +1598,6 @@ class CGSolverHIP:
             res.rnrm2 = math.sqrt(max(gamma_host, 0.0))
         res.converged = converged
         nnz_full = self.local.nnzA + self.local.nnzO
-        res.nflops = res.niterations * (cg_flops_per_iter(nnz_full, n) + 8.0 * n)
-        res.halo_bytes_sent = self.halo.bytes_sent
-        res.halo_msgs_sent = self.halo.nmsgs_sent
-        self.niterations_total += res.niterations
-        if self.prof.enabled:
-            from .profiling import annotate_op_stats
-
-            idxb = None
-            if self.matfree is not None:
-                idxb = -8.0  # matrix-free: no vals (8 B) and no cols read
-            elif self.bsell is not None:
-                idxb = 4.0 / (self.bsell[3] ** 2)
-            annotate_op_stats(res, self.local, self.prof.collect(),
-                              idx_bytes_per_nnz=idxb)
-            self.prof.reset()
+        self._count_work(res, cg_flops_per_iter(nnz_full, n) + 8.0 * n)
+        self._annotate_profile(res)
         return res

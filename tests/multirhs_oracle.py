@@ -316,3 +316,64 @@ def run_reduce(ops, pvals, k, dev, scal0, slot, accumulate):
     ss = ko._np(scal)
     assert np.array_equal(_bits(ko._np(partials)), _bits(part)), "partials modified"
     return [_scal_got({}, ss[c]) for c in range(k)], {"scal": ss}
+
+
+# ---------------------------------------------------------------------------
+# solver level: runs shorter than the host test's lag
+
+SHORT_MAXITS = (0, 1, 2, 3)
+
+
+@lru_cache(maxsize=None)
+def short_run_system():
+    """(S, B) for solves that stop at maxits <= 3, where the lag-2 host test
+    reads everything in its tail drain: the 648-row 6x6x6 queen_like_spec(3)
+    system (one rank: the SpMM fast path) and three default_rng(5) columns,
+    a group that is padded to K = 4."""
+    from acg_amd.gen import queen_like_spec, stencil_local_slab
+
+    S = stencil_local_slab(6, 6, 6, queen_like_spec(3), 0, 1)
+    assert S.nowned == 648 and S.nghost == 0
+    B = np.random.default_rng(5).standard_normal((S.nowned, 3))
+    B.setflags(write=False)
+    return S, B
+
+
+@lru_cache(maxsize=None)
+def short_run_cpu(method, maxits):
+    """CGSolverCPU.solve_multi / solve_block on short_run_system with
+    res_rtol = 0, so that only maxits stops it: (X, results)."""
+    import torch
+
+    from acg_amd.solvers.cpu import CGSolverCPU
+
+    S, B = short_run_system()
+    X = torch.zeros(S.nowned, B.shape[1], dtype=torch.float64)
+    res = getattr(CGSolverCPU(S), method)(torch.from_numpy(B.copy()), X,
+                                          maxits=maxits, res_rtol=0.0)
+    return X, res
+
+
+def check_short_run(method, maxits, dev):
+    """CGSolverHIP.<method> stopped by maxits <= 3 against the CPU oracle:
+    every column reports exactly maxits iterations, unconverged, without a
+    breakdown, and X agrees to the criterion of the longer solver tests."""
+    import torch
+
+    from acg_amd.solvers.hip import CGSolverHIP
+
+    S, B = short_run_system()
+    Xc, resc = short_run_cpu(method, maxits)
+    assert all(r.niterations == maxits and not r.converged
+               and r.block_breakdown == -1 for r in resc)
+    solver = CGSolverHIP(S, device=dev)
+    assert solver._multi_fast_path()
+    X = torch.zeros(S.nowned, B.shape[1], dtype=torch.float64, device=dev)
+    res = getattr(solver, method)(torch.from_numpy(B.copy()).to(dev), X,
+                                  maxits=maxits, res_rtol=0.0)
+    assert len(res) == B.shape[1]
+    for c, r in enumerate(res):
+        assert r.niterations == maxits, (c, r.summary())
+        assert r.converged is False, (c, r.summary())
+        assert r.block_breakdown == -1, (c, r.summary())
+    torch.testing.assert_close(X.cpu(), Xc, rtol=1e-6, atol=1e-8)

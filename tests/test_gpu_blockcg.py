@@ -10,6 +10,7 @@ import torch
 
 import blockcg_oracle as bo
 import kernel_oracle as ko
+import multirhs_oracle as mo
 
 pytestmark = pytest.mark.gpu
 
@@ -337,6 +338,13 @@ def test_handover_in_the_first_iteration(dev, system):
     assert all(r.converged and r.block_breakdown == 1 for r in res)
     bo.check_true_residual(S, Be, X, f"{name} exact")
     _agrees_with_single(S, Be, X, solver, dev)
+
+
+@pytest.mark.parametrize("maxits", mo.SHORT_MAXITS)
+def test_solve_block_stopped_within_the_lag(dev, maxits):
+    """maxits <= 3: the lag-2 host test reads everything in its tail drain
+    (maxits <= 2) or one state in the loop and the rest in the drain."""
+    mo.check_short_run("solve_block", maxits, dev)
 
 
 def test_csr_and_k1_are_solve_multi(dev, system):

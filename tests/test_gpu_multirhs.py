@@ -334,6 +334,13 @@ def test_solve_multi_groups_of_four(dev, system, single_solves):
         solver.solve_multi(Bk, X)
 
 
+@pytest.mark.parametrize("maxits", mo.SHORT_MAXITS)
+def test_solve_multi_stopped_within_the_lag(dev, maxits):
+    """maxits <= 3: the lag-2 host test reads everything in its tail drain
+    (maxits <= 2) or one value in the loop and the rest in the drain."""
+    mo.check_short_run("solve_multi", maxits, dev)
+
+
 def test_solve_multi_csr_falls_back(dev, system, single_solves):
     from acg_amd.solvers.hip import CGSolverHIP
 

@@ -50,8 +50,9 @@ def make_parser() -> argparse.ArgumentParser:
     p.add_argument("--seed", type=int, default=0, help="partitioner seed")
     p.add_argument("--solver", default=None,
                    choices=("acg", "acg-pipelined", "acg-device",
-                            "acg-jacobi", "acg-mixed", "acg-block", "cpu",
-                            "cpu-pipelined", "cpu-jacobi", "cpu-mixed",
+                            "acg-jacobi", "acg-bjacobi", "acg-mixed",
+                            "acg-block", "cpu", "cpu-pipelined",
+                            "cpu-jacobi", "cpu-bjacobi", "cpu-mixed",
                             "cpu-block", "scipy",
                             "scipy-pipelined",
                             "petsc", "petsc-pipelined"),
@@ -412,6 +413,9 @@ def main(argv=None) -> int:
                 elif solver_name == "acg-jacobi":
                     solver.solve_jacobi(b, x.clone(), maxits=args.warmup,
                                         res_rtol=0.0)
+                elif solver_name == "acg-bjacobi":
+                    solver.solve_bjacobi(b, x.clone(), maxits=args.warmup,
+                                         res_rtol=0.0)
                 elif solver_name == "acg-mixed":
                     solver.solve_mixed(b, x.clone(), maxits=args.warmup,
                                        res_rtol=0.0, **mixed_kw)
@@ -432,6 +436,10 @@ def main(argv=None) -> int:
                 res = solver.solve_jacobi(b, x, maxits=args.max_iterations,
                                           res_atol=args.residual_atol,
                                           res_rtol=args.residual_rtol)
+            elif solver_name == "acg-bjacobi":
+                res = solver.solve_bjacobi(b, x, maxits=args.max_iterations,
+                                           res_atol=args.residual_atol,
+                                           res_rtol=args.residual_rtol)
             elif solver_name == "acg-mixed":
                 res = solver.solve_mixed(b, x, maxits=args.max_iterations,
                                          res_atol=args.residual_atol,
@@ -464,6 +472,10 @@ def main(argv=None) -> int:
                 res = solver.solve_jacobi(b, x, maxits=args.max_iterations,
                                           res_atol=args.residual_atol,
                                           res_rtol=args.residual_rtol)
+            elif solver_name == "cpu-bjacobi":
+                res = solver.solve_bjacobi(b, x, maxits=args.max_iterations,
+                                           res_atol=args.residual_atol,
+                                           res_rtol=args.residual_rtol)
             elif solver_name == "cpu-mixed":
                 if args.diff_atol > 0 or args.diff_rtol > 0:
                     raise AcgError(ErrCode.NOT_SUPPORTED,

@@ -373,6 +373,117 @@ def pcg_fused_update(r, x, p, t, z, dinv, scal, partials, n: int) -> None:
                        partials.data_ptr(), _stream())
 
 
+# -- block-Jacobi PCG on Block-SELL operators --------------------------------
+
+BJ_DOFS = (2, 3, 4)
+
+
+def block_inv_len(nnodes: int, dof: int) -> int:
+    """Length of the packed inverse-block buffer: dof(dof+1)/2 components
+    per node, laid out [slice][component][64]."""
+    return ((nnodes + 63) // 64) * (dof * (dof + 1) // 2) * 64
+
+
+def _bj_check(what: str, n: int, dof: int, minv: torch.Tensor, *vecs) -> int:
+    """Validate the arguments shared by the block-Jacobi ops (before any
+    launch); returns nnodes."""
+    if dof not in BJ_DOFS:
+        raise ValueError(f"{what}: dof must be one of {BJ_DOFS}, got {dof}")
+    if n < 0 or n % dof:
+        raise ValueError(f"{what}: n={n} is not a multiple of dof={dof}")
+    nnodes = n // dof
+    for v in (minv, *vecs):
+        if v.dtype != torch.float64:
+            raise TypeError(f"{what}: vectors must be float64, got {v.dtype}")
+        if not v.is_cuda or v.device != minv.device:
+            raise ValueError(f"{what}: tensors must live on one GPU")
+        if not v.is_contiguous():
+            raise ValueError(f"{what}: tensors must be contiguous")
+    for v in vecs:
+        if v.dim() != 1 or v.numel() < n:
+            raise ValueError(f"{what}: vector has shape {tuple(v.shape)}, "
+                             f"needs at least {n} entries")
+    if minv.numel() != block_inv_len(nnodes, dof):
+        raise ValueError(f"{what}: inverse buffer has {minv.numel()} entries, "
+                         f"needs {block_inv_len(nnodes, dof)} for "
+                         f"{nnodes} nodes of dof {dof}")
+    return nnodes
+
+
+def _bj_slab(what: str, scal: torch.Tensor, partials: torch.Tensor,
+             device) -> None:
+    for v, need in ((scal, S_NSLOTS), (partials, 2 * MAXG)):
+        if (v.dtype != torch.float64 or v.device != device
+                or not v.is_contiguous() or v.numel() < need):
+            raise ValueError(f"{what}: scal/partials must be contiguous "
+                             f"float64 on {device} with >= {S_NSLOTS} / "
+                             f"{2 * MAXG} entries")
+
+
+def bsell_diag_inv(bptr: torch.Tensor, bcol: torch.Tensor,
+                   bvals: torch.Tensor, nnodes: int, dof: int):
+    """Inverse of every node's dof x dof diagonal block of a Block-SELL
+    matrix, by Cholesky, as packed upper triangles (see block_inv_len).
+    Returns (minv, nbad); nbad counts the nodes without a diagonal block
+    or with a pivot that is <= 0 or not finite (their inverse is zero).
+    One launch plus one host read of the status word."""
+    what = "bsell_diag_inv"
+    if dof not in BJ_DOFS:
+        raise ValueError(f"{what}: dof must be one of {BJ_DOFS}, got {dof}")
+    if bvals.dtype != torch.float64:
+        raise TypeError(f"{what}: reads the float64 block values, "
+                        f"got {bvals.dtype}")
+    if bptr.dtype != torch.int64 or bcol.dtype != torch.int32:
+        raise TypeError(f"{what}: bptr must be int64 and bcol int32")
+    for v in (bptr, bcol, bvals):
+        if not v.is_cuda or v.device != bvals.device:
+            raise ValueError(f"{what}: tensors must live on one GPU")
+        if not v.is_contiguous():
+            raise ValueError(f"{what}: tensors must be contiguous")
+    nslices = bptr.numel() - 1
+    if nnodes < 0 or nslices != (nnodes + 63) // 64:
+        raise ValueError(f"{what}: {nslices} slices do not hold {nnodes} nodes")
+    if (bvals.numel() != bcol.numel() * dof * dof
+            or (nslices > 0 and bcol.numel() % 64)):
+        raise ValueError(f"{what}: {bcol.numel()} block columns do not match "
+                         f"{bvals.numel()} values of dof {dof}")
+    if nslices > 0 and int(bptr[-1]) != bcol.numel():  # setup-time read
+        raise ValueError(f"{what}: bptr ends at {int(bptr[-1])}, but there "
+                         f"are {bcol.numel()} block columns")
+    minv = torch.zeros(block_inv_len(nnodes, dof), dtype=torch.float64,
+                       device=bvals.device)
+    status = torch.zeros(1, dtype=torch.int32, device=bvals.device)
+    if nnodes > 0:
+        K.bsell_diag_inv(nslices, nnodes, dof, bptr.data_ptr(),
+                         bcol.data_ptr(), bvals.data_ptr(), minv.data_ptr(),
+                         status.data_ptr(), _stream())
+    return minv, int(status.item())
+
+
+def bjacobi_apply(minv: torch.Tensor, r: torch.Tensor, z: torch.Tensor,
+                  partials: torch.Tensor, scal: torch.Tensor, n: int,
+                  dof: int) -> None:
+    """z = M^-1 r with the packed inverse blocks of bsell_diag_inv; rotates
+    S_RR -> S_RR_PREV and publishes (r,z) in S_RR and (r,r) in S_GAMMA
+    (the finalize of pcg_fused_update)."""
+    nnodes = _bj_check("bjacobi_apply", n, dof, minv, r, z)
+    _bj_slab("bjacobi_apply", scal, partials, minv.device)
+    K.bjacobi_apply(minv.data_ptr(), r.data_ptr(), z.data_ptr(), nnodes, dof,
+                    scal.data_ptr(), partials.data_ptr(), _stream())
+
+
+def bpcg_fused_update(r, x, p, t, z, minv, scal, partials, n: int,
+                      dof: int) -> None:
+    """Block-Jacobi PCG fused epilogue: alpha = rz/pt (device); r -= alpha t;
+    x += alpha p; z = M^-1 r node by node; rotates rz -> RR_PREV and
+    publishes the new rz in S_RR plus the TRUE (r,r) in S_GAMMA."""
+    nnodes = _bj_check("bpcg_fused_update", n, dof, minv, r, x, p, t, z)
+    _bj_slab("bpcg_fused_update", scal, partials, minv.device)
+    K.bpcg_fused_update(r.data_ptr(), x.data_ptr(), p.data_ptr(),
+                        t.data_ptr(), z.data_ptr(), minv.data_ptr(), nnodes,
+                        dof, scal.data_ptr(), partials.data_ptr(), _stream())
+
+
 def sell_pipe(sellptr, cols, vals, nrows_pass: int, rowbase: int,
               border_base: int, w_old, qpart, z, t, p, x, r, w_new,
               scal, first: bool, partials, partials_off: int,

@@ -564,6 +564,205 @@ k_pcg_finalize(const double* __restrict__ partials, int nblocks,
     }
 }
 
+// ---------------------------------------------------------------------------
+// Block-Jacobi PCG on Block-SELL operators (beyond reference, opt-in):
+// M = blockdiag(A_node,node), the dof x dof diagonal block of every node.
+// The inverse blocks are symmetric and stored as their packed upper
+// triangle, NC = dof(dof+1)/2 doubles per node, row-major over (a <= b),
+// laid out [slice][component][64]: component c of lane's node sits at
+//   (s*NC + c)*64 + lane
+// so every component is one contiguous 512 B wave load.  One lane per node
+// throughout (the mapping of k_spmv_bsell); r/t/x/p/z are touched at
+// stride dof per lane like that kernel's y write.
+__host__ __device__ constexpr int bj_tri(int a, int b, int dof) {
+    // packed-upper index of (a, b), a <= b
+    return a * dof - a * (a - 1) / 2 + (b - a);
+}
+
+// setup: sum every block of the node's list whose bcol is the node itself
+// (the self block plus any zero-valued padding blocks -- both packers pad
+// short nodes with zero blocks that name the node, k_stencil_bfill after
+// the real blocks and bsell_from_csr wherever the node's list ends, so a
+// sum is right under either and does not depend on block order), factor
+// it M = L L^T and store M^-1 = L^-T L^-1.  A node without a diagonal
+// block, or with a pivot that is <= 0 or not finite, counts into *status
+// (integer atomic: order-independent) and gets a zero inverse.  Lanes past
+// nnodes in the last slice do nothing.  Always reads the fp64 bvals.
+template <int DOF>
+__global__ void __launch_bounds__(BLOCK)
+k_bsell_diag_inv(long nslices, long nnodes,
+                 const long* __restrict__ bptr,
+                 const int* __restrict__ bcol,
+                 const double* __restrict__ bvals,
+                 double* __restrict__ minv,
+                 int* __restrict__ status) {
+    constexpr int D2 = DOF * DOF;
+    constexpr int NC = DOF * (DOF + 1) / 2;
+    const int lane = threadIdx.x & (WAVE - 1);
+    const long wslice = ((long)blockIdx.x * BLOCK + threadIdx.x) >> 6;
+    const long nw = ((long)gridDim.x * BLOCK) >> 6;
+    for (long s = wslice; s < nslices; s += nw) {
+        const long node = s * WAVE + lane;
+        if (node >= nnodes) continue;
+        const long b0 = bptr[s];
+        const long blen = (bptr[s + 1] - b0) >> 6;
+        const int* __restrict__ c = bcol + b0 + lane;
+        const double* __restrict__ v = bvals + b0 * D2;
+        double d[D2];
+        #pragma unroll
+        for (int k = 0; k < D2; ++k) d[k] = 0.0;
+        int found = 0;
+        for (long j = 0; j < blen; ++j) {
+            if ((long)c[j * WAVE] != node) continue;
+            ++found;
+            const double* __restrict__ vj = v + j * D2 * WAVE;
+            #pragma unroll
+            for (int k = 0; k < D2; ++k) d[k] += vj[bval_off<D2>(k, lane)];
+        }
+        // Cholesky of the lower triangle
+        bool ok = found > 0;
+        double l[DOF][DOF];
+        #pragma unroll
+        for (int j = 0; j < DOF; ++j) {
+            double piv = d[j * DOF + j];
+            #pragma unroll
+            for (int q = 0; q < j; ++q) piv -= l[j][q] * l[j][q];
+            ok = ok && piv > 0.0 && piv <= 1.79769313486231570815e308;
+            const double ljj = sqrt(piv);
+            l[j][j] = ljj;
+            #pragma unroll
+            for (int i = j + 1; i < DOF; ++i) {
+                double t = d[i * DOF + j];
+                #pragma unroll
+                for (int q = 0; q < j; ++q) t -= l[i][q] * l[j][q];
+                l[i][j] = t / ljj;
+            }
+        }
+        // li = L^-1 (lower triangular), column by column
+        double li[DOF][DOF];
+        #pragma unroll
+        for (int cc = 0; cc < DOF; ++cc) {
+            #pragma unroll
+            for (int i = cc; i < DOF; ++i) {
+                double t = (i == cc) ? 1.0 : 0.0;
+                #pragma unroll
+                for (int q = cc; q < i; ++q) t -= l[i][q] * li[q][cc];
+                li[i][cc] = t / l[i][i];
+            }
+        }
+        // M^-1(a, b) = sum_{k >= b} li[k][a] * li[k][b],  a <= b
+        double* __restrict__ out = minv + s * (NC * WAVE) + lane;
+        #pragma unroll
+        for (int a = 0; a < DOF; ++a) {
+            #pragma unroll
+            for (int b = a; b < DOF; ++b) {
+                double t = 0.0;
+                #pragma unroll
+                for (int k = b; k < DOF; ++k) t += li[k][a] * li[k][b];
+                out[bj_tri(a, b, DOF) * WAVE] = ok ? t : 0.0;
+            }
+        }
+        if (!ok) atomicAdd(status, 1);
+    }
+}
+
+template <int DOF>
+__device__ __forceinline__ void bj_load_inv(const double* __restrict__ minv,
+                                            long node,
+                                            double (&m)[DOF * (DOF + 1) / 2]) {
+    constexpr int NC = DOF * (DOF + 1) / 2;
+    const double* __restrict__ q = minv + (node >> 6) * (NC * WAVE) + (node & (WAVE - 1));
+    #pragma unroll
+    for (int c = 0; c < NC; ++c) m[c] = q[c * WAVE];
+}
+
+// z = M^-1_node r  (row a: sum over b in ascending order)
+template <int DOF>
+__device__ __forceinline__ void bj_mul(const double (&m)[DOF * (DOF + 1) / 2],
+                                       const double (&r)[DOF], double (&z)[DOF]) {
+    #pragma unroll
+    for (int a = 0; a < DOF; ++a) {
+        double acc = 0.0;
+        #pragma unroll
+        for (int b = 0; b < DOF; ++b)
+            acc += m[a <= b ? bj_tri(a, b, DOF) : bj_tri(b, a, DOF)] * r[b];
+        z[a] = acc;
+    }
+}
+
+// z = M^-1 r with the partials of (r,z) and (r,r) in the two halves of
+// the scratch (k_pcg_finalize's layout): z0 of the block-Jacobi PCG
+template <int DOF>
+__global__ void __launch_bounds__(BLOCK)
+k_bjacobi_apply(const double* __restrict__ minv, const double* __restrict__ r,
+                double* __restrict__ z, long nnodes,
+                double* __restrict__ partials) {
+    double arz = 0.0, arr = 0.0;
+    const long stride = (long)gridDim.x * BLOCK;
+    for (long i = (long)blockIdx.x * BLOCK + threadIdx.x; i < nnodes; i += stride) {
+        double rv[DOF], zv[DOF], m[DOF * (DOF + 1) / 2];
+        #pragma unroll
+        for (int a = 0; a < DOF; ++a) rv[a] = r[i * DOF + a];
+        bj_load_inv<DOF>(minv, i, m);
+        bj_mul<DOF>(m, rv, zv);
+        #pragma unroll
+        for (int a = 0; a < DOF; ++a) {
+            z[i * DOF + a] = zv[a];
+            arz += rv[a] * zv[a];
+            arr += rv[a] * rv[a];
+        }
+    }
+    arz = block_reduce(arz);
+    __syncthreads();  // block_reduce reuses its LDS scratch
+    arr = block_reduce(arr);
+    if (threadIdx.x == 0) {
+        partials[blockIdx.x] = arz;
+        partials[MAXG + blockIdx.x] = arr;
+    }
+}
+
+// block form of k_pcg_fused_update: alpha = rz/(p,t) from the device slab,
+// r -= alpha t, x += alpha p, z_node = M^-1_node r'_node from the new r in
+// registers, partials of rz' and rr'.  Same non-temporal choices: t and x
+// are single-use, r/z/p stay cacheable.  Traffic: 7n vector doubles plus
+// (dof+1)/2 n of packed inverse (9n for dof 3 against point Jacobi's 8n).
+template <int DOF>
+__global__ void __launch_bounds__(BLOCK)
+k_bpcg_fused_update(double* __restrict__ r, double* __restrict__ x,
+                    const double* __restrict__ p, const double* __restrict__ t,
+                    double* __restrict__ z, const double* __restrict__ minv,
+                    long nnodes, const double* __restrict__ scal,
+                    double* __restrict__ partials) {
+    const double alpha = safe_div(scal[S_RR], scal[S_PT]);  // S_RR = rz
+    double arz = 0.0, arr = 0.0;
+    const long stride = (long)gridDim.x * BLOCK;
+    for (long i = (long)blockIdx.x * BLOCK + threadIdx.x; i < nnodes; i += stride) {
+        double rn[DOF], zv[DOF], m[DOF * (DOF + 1) / 2];
+        #pragma unroll
+        for (int a = 0; a < DOF; ++a) {
+            const long e = i * DOF + a;
+            rn[a] = r[e] - alpha * ld_nt(t + e);
+            r[e] = rn[a];
+            __builtin_nontemporal_store(ld_nt(x + e) + alpha * p[e], x + e);
+        }
+        bj_load_inv<DOF>(minv, i, m);
+        bj_mul<DOF>(m, rn, zv);
+        #pragma unroll
+        for (int a = 0; a < DOF; ++a) {
+            z[i * DOF + a] = zv[a];
+            arz += rn[a] * zv[a];
+            arr += rn[a] * rn[a];
+        }
+    }
+    arz = block_reduce(arz);
+    __syncthreads();  // block_reduce reuses its LDS scratch
+    arr = block_reduce(arr);
+    if (threadIdx.x == 0) {
+        partials[blockIdx.x] = arz;
+        partials[MAXG + blockIdx.x] = arr;
+    }
+}
+
 // dot: partials[b] = block sum of x[i]*y[i]
 __global__ void __launch_bounds__(BLOCK)
 k_dot(const double* __restrict__ x, const double* __restrict__ y, long n,
@@ -2684,6 +2883,67 @@ void pcg_fused_update(uintptr_t r, uintptr_t x, uintptr_t p, uintptr_t t,
     check_hip("pcg_finalize");
 }
 
+// block-Jacobi: one thread per node, ~2 nodes per thread before the cap
+static inline long bj_grid(long nnodes) { return elem_grid(nnodes, 2); }
+
+#define DISPATCH_DOF(dof, WHAT, MACRO) \
+    switch (dof) { \
+        case 2: MACRO(2); break; \
+        case 3: MACRO(3); break; \
+        case 4: MACRO(4); break; \
+        default: throw std::runtime_error(WHAT ": dof must be 2/3/4"); \
+    }
+
+void bsell_diag_inv(long nslices, long nnodes, int dof, uintptr_t bptr,
+                    uintptr_t bcol, uintptr_t bvals, uintptr_t minv,
+                    uintptr_t status, uintptr_t stream) {
+    if (nnodes == 0) return;
+    long blocks = (nslices * WAVE + BLOCK - 1) / BLOCK;
+    if (blocks > MAXG) blocks = MAXG;
+    #define LDI(D) \
+        hipLaunchKernelGGL((k_bsell_diag_inv<D>), dim3((unsigned)blocks), \
+            dim3(BLOCK), 0, S(stream), nslices, nnodes, (const long*)bptr, \
+            (const int*)bcol, (const double*)bvals, (double*)minv, (int*)status)
+    DISPATCH_DOF(dof, "bsell_diag_inv", LDI)
+    #undef LDI
+    check_hip("bsell_diag_inv");
+}
+
+void bjacobi_apply(uintptr_t minv, uintptr_t r, uintptr_t z, long nnodes,
+                   int dof, uintptr_t scal, uintptr_t partials,
+                   uintptr_t stream) {
+    long blocks = bj_grid(nnodes);
+    #define LBA(D) \
+        hipLaunchKernelGGL((k_bjacobi_apply<D>), dim3((unsigned)blocks), \
+            dim3(BLOCK), 0, S(stream), (const double*)minv, (const double*)r, \
+            (double*)z, nnodes, (double*)partials)
+    DISPATCH_DOF(dof, "bjacobi_apply", LBA)
+    #undef LBA
+    check_hip("bjacobi_apply");
+    hipLaunchKernelGGL(k_pcg_finalize, dim3(1), dim3(BLOCK), 0, S(stream),
+                       (const double*)partials, (int)blocks, (double*)scal);
+    check_hip("bjacobi_apply_finalize");
+}
+
+void bpcg_fused_update(uintptr_t r, uintptr_t x, uintptr_t p, uintptr_t t,
+                       uintptr_t z, uintptr_t minv, long nnodes, int dof,
+                       uintptr_t scal, uintptr_t partials, uintptr_t stream) {
+    long blocks = bj_grid(nnodes);
+    #define LBU(D) \
+        hipLaunchKernelGGL((k_bpcg_fused_update<D>), dim3((unsigned)blocks), \
+            dim3(BLOCK), 0, S(stream), (double*)r, (double*)x, \
+            (const double*)p, (const double*)t, (double*)z, \
+            (const double*)minv, nnodes, (const double*)scal, \
+            (double*)partials)
+    DISPATCH_DOF(dof, "bpcg_fused_update", LBU)
+    #undef LBU
+    check_hip("bpcg_fused_update");
+    hipLaunchKernelGGL(k_pcg_finalize, dim3(1), dim3(BLOCK), 0, S(stream),
+                       (const double*)partials, (int)blocks, (double*)scal);
+    check_hip("bpcg_finalize");
+}
+#undef DISPATCH_DOF
+
 void cg_fused_update(uintptr_t r, uintptr_t x, uintptr_t p, uintptr_t t, long n,
                      uintptr_t scal, uintptr_t partials, uintptr_t stream) {
     long blocks = elem_grid(n);
@@ -3074,6 +3334,9 @@ PYBIND11_MODULE(_acg_kernels, m) {
     m.def("daypx_ratio", &daypx_ratio);
     m.def("cg_fused_update", &cg_fused_update);
     m.def("pcg_fused_update", &pcg_fused_update);
+    m.def("bsell_diag_inv", &bsell_diag_inv);
+    m.def("bjacobi_apply", &bjacobi_apply);
+    m.def("bpcg_fused_update", &bpcg_fused_update);
     m.def("pipelined_fused", &pipelined_fused);
     m.def("sell_pipe", &sell_pipe);
     m.def("pipelined_finalize", &pipelined_finalize);

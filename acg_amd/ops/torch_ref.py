@@ -464,6 +464,138 @@ def pcg_fused_update(r, x, p, t, z, dinv, scal, partials, n) -> None:
     scal[S_GAMMA] = torch.dot(r[:n], r[:n])
 
 
+# -- block-Jacobi PCG on Block-SELL operators (same buffer layout as
+# gpu_ops: dof(dof+1)/2 packed-upper components per node, row-major over
+# (a <= b), stored [slice][component][64])
+
+BJ_DOFS = (2, 3, 4)
+
+
+def block_inv_len(nnodes: int, dof: int, C: int = 64) -> int:
+    return ((nnodes + C - 1) // C) * (dof * (dof + 1) // 2) * C
+
+
+def _bj_pairs(dof: int):
+    return [(a, b) for a in range(dof) for b in range(a, dof)]
+
+
+def unpack_block_inv(minv, nnodes: int, dof: int, C: int = 64):
+    """Packed inverse blocks -> dense symmetric (nnodes, dof, dof)."""
+    nc = dof * (dof + 1) // 2
+    nslices = (nnodes + C - 1) // C
+    if minv.numel() != nslices * nc * C:
+        raise ValueError(f"unpack_block_inv: buffer has {minv.numel()} "
+                         f"entries, needs {nslices * nc * C}")
+    comp = minv.view(nslices, nc, C).permute(0, 2, 1).reshape(nslices * C, nc)
+    out = torch.zeros(nnodes, dof, dof, dtype=minv.dtype, device=minv.device)
+    for c, (a, b) in enumerate(_bj_pairs(dof)):
+        out[:, a, b] = comp[:nnodes, c]
+        out[:, b, a] = comp[:nnodes, c]
+    return out
+
+
+def pack_block_inv(blocks, C: int = 64):
+    """Dense symmetric (nnodes, dof, dof) -> packed buffer (upper triangle
+    taken); entries of the lanes past nnodes are zero."""
+    nnodes, dof = blocks.shape[0], blocks.shape[1]
+    nc = dof * (dof + 1) // 2
+    nslices = (nnodes + C - 1) // C
+    comp = torch.zeros(nslices * C, nc, dtype=blocks.dtype,
+                       device=blocks.device)
+    for c, (a, b) in enumerate(_bj_pairs(dof)):
+        comp[:nnodes, c] = blocks[:, a, b]
+    return comp.view(nslices, C, nc).permute(0, 2, 1).contiguous().view(-1)
+
+
+def bsell_diag_blocks(bptr, bcol, bvals, nnodes: int, dof: int, C: int = 64):
+    """(sum of every block of node i whose block column is i, how many
+    such blocks there are) as (nnodes, dof, dof) and (nnodes,) tensors."""
+    D2 = dof * dof
+    even = D2 & ~1
+    nslices = bptr.numel() - 1
+    assert (nnodes + C - 1) // C == nslices, \
+        f"BSELL structure was built with a different chunk size than C={C}"
+    dev = bvals.device
+    blocks = torch.zeros(nslices * C, D2, dtype=torch.float64, device=dev)
+    found = torch.zeros(nslices * C, dtype=torch.int64, device=dev)
+    lanes = torch.arange(C, device=dev)
+    for s in range(nslices):
+        b0 = int(bptr[s])
+        L = (int(bptr[s + 1]) - b0) // C
+        if not L:
+            continue
+        cb = bcol[b0:b0 + L * C].view(L, C).long()
+        hit = cb == (s * C + lanes)[None, :]
+        found[s * C:(s + 1) * C] = hit.sum(dim=0)
+        v = bvals[b0 * D2:(b0 + L * C) * D2].view(L, D2 * C)
+        for k in range(D2):
+            if k < even:
+                lo = (k >> 1) * 2 * C + (k & 1)
+                a = v[:, lo:(k >> 1) * 2 * C + 2 * C:2]
+            else:
+                a = v[:, even * C:even * C + C]
+            blocks[s * C:(s + 1) * C, k] = (a * hit).sum(dim=0)
+    return blocks[:nnodes].view(nnodes, dof, dof), found[:nnodes]
+
+
+def bsell_diag_inv(bptr, bcol, bvals, nnodes: int, dof: int):
+    """Matches k_bsell_diag_inv: (packed inverse of every node's summed
+    diagonal block, number of bad nodes).  A node is bad without a diagonal
+    block or when a Cholesky pivot is <= 0 or not finite; its inverse is
+    zero."""
+    if dof not in BJ_DOFS:
+        raise ValueError(f"bsell_diag_inv: dof must be one of {BJ_DOFS}, "
+                         f"got {dof}")
+    if bvals.dtype != torch.float64:
+        raise TypeError(f"bsell_diag_inv: reads the float64 block values, "
+                        f"got {bvals.dtype}")
+    if nnodes == 0:
+        return torch.zeros(0, dtype=torch.float64, device=bvals.device), 0
+    D, found = bsell_diag_blocks(bptr, bcol, bvals, nnodes, dof)
+    Lf, info = torch.linalg.cholesky_ex(D)
+    ok = (found > 0) & (info == 0) & torch.isfinite(Lf).all(dim=(1, 2))
+    eye = torch.eye(dof, dtype=torch.float64, device=D.device).expand_as(D)
+    Lf = torch.where(ok[:, None, None], Lf, eye)
+    inv = torch.cholesky_inverse(Lf)
+    inv = torch.where(ok[:, None, None], inv, torch.zeros_like(inv))
+    return pack_block_inv(inv), int((~ok).sum())
+
+
+def _bj_mul(minv, v, n: int, dof: int):
+    nnodes = n // dof
+    if dof not in BJ_DOFS or n % dof:
+        raise ValueError(f"block Jacobi: n={n} must be a multiple of dof "
+                         f"in {BJ_DOFS}, got dof={dof}")
+    if minv.numel() != block_inv_len(nnodes, dof):
+        raise ValueError(f"block Jacobi: inverse buffer has {minv.numel()} "
+                         f"entries, needs {block_inv_len(nnodes, dof)}")
+    Mi = unpack_block_inv(minv, nnodes, dof)
+    return torch.einsum("nab,nb->na", Mi, v[:n].view(nnodes, dof)).reshape(n)
+
+
+def bjacobi_apply(minv, r, z, partials, scal, n: int, dof: int) -> None:
+    """z = M^-1 r; rotate S_RR -> S_RR_PREV, publish (r,z) in S_RR and
+    (r,r) in S_GAMMA (matches k_bjacobi_apply + k_pcg_finalize)."""
+    z[:n] = _bj_mul(minv, r, n, dof)
+    scal[S_RR_PREV] = scal[S_RR].clone()
+    scal[S_RR] = torch.dot(r[:n], z[:n])
+    scal[S_GAMMA] = torch.dot(r[:n], r[:n])
+
+
+def bpcg_fused_update(r, x, p, t, z, minv, scal, partials, n: int,
+                      dof: int) -> None:
+    """Block-Jacobi PCG epilogue: alpha = rz/pt; update r,x; z = M^-1 r;
+    rotate rz -> rr_prev and publish the new rz in S_RR and the true (r,r)
+    in S_GAMMA (matches k_bpcg_fused_update + k_pcg_finalize)."""
+    alpha = _sdiv(float(scal[S_RR]), float(scal[S_PT]))
+    r[:n] -= alpha * t[:n]
+    x[:n] += alpha * p[:n]
+    z[:n] = _bj_mul(minv, r, n, dof)
+    scal[S_RR_PREV] = scal[S_RR].clone()
+    scal[S_RR] = torch.dot(r[:n], z[:n])
+    scal[S_GAMMA] = torch.dot(r[:n], r[:n])
+
+
 def _pipelined_coeffs(scal, first: bool):
     gamma = float(scal[S_GAMMA])
     delta = float(scal[S_DELTA])

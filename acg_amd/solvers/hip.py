@@ -1305,6 +1305,126 @@ class CGSolverHIP:
         self._count_work(res, cg_flops_per_iter(nnz_full, n) + 3.0 * n)
         return res
 
+    # -- block-Jacobi PCG on Block-SELL operators (beyond reference,
+    # opt-in, never auto-selected) ----------------------------------------
+
+    def _block_inverse(self) -> torch.Tensor:
+        """Packed inverse diagonal blocks of the Block-SELL matA, built on
+        the GPU once per solver instance (one launch + one status read)."""
+        from ..utils.errors import AcgError, ErrCode
+
+        if self.bsell is None:
+            raise AcgError(ErrCode.NOT_SUPPORTED,
+                           "block Jacobi needs a Block-SELL operator (dense "
+                           "dof x dof node blocks, dof 2/3/4); this system "
+                           f"uses {self._format_name()}")
+        if "bjacobi_minv" not in self._ws:
+            bptr, bcol, bvals, dof = self.bsell
+            minv, nbad = ops.bsell_diag_inv(bptr, bcol, bvals,
+                                            self.n // dof, dof)
+            if nbad > 0:
+                raise AcgError(ErrCode.INVALID_VALUE,
+                               f"block Jacobi: {nbad} nodes have a missing "
+                               f"or not positive definite diagonal block")
+            self._ws["bjacobi_minv"] = minv
+        return self._ws["bjacobi_minv"]
+
+    def solve_bjacobi(self, b: torch.Tensor, x: torch.Tensor,
+                      maxits: int = 100, res_atol: float = 0.0,
+                      res_rtol: float = 1e-9) -> SolveResult:
+        """Block-Jacobi PCG: M = blockdiag of the dof x dof node blocks of
+        the Block-SELL operator, inverted on the GPU at the first solve
+        (file-extracted and device-generated systems alike).  The algebra
+        of :meth:`solve_jacobi` with z_node = M_node^-1 r_node inside the
+        fused update; the SpMV with its fused (p,t) and every reduced slot
+        take the paths of the other solvers.  Convergence is tested on the
+        TRUE (r,r) (S_GAMMA) through the lag-2 ring of :meth:`solve`: the
+        host never blocks on an iteration's tail, and ``niterations`` is
+        the first iteration whose rr met the tolerance.  Eager (no graph
+        capture)."""
+        minv = self._block_inverse()
+        dof = self.bsell[3]
+        res = SolveResult(solver="cg-hip-bjacobi", maxits=maxits,
+                          res_atol=res_atol, res_rtol=res_rtol,
+                          nranks=self.comm.size if self.comm else 1)
+        n = self.n
+        S = ops
+        scal = self.scal
+        ws = self._workspace("bjacobi", [("r", False), ("t", False),
+                                         ("z", False), ("p", True),
+                                         ("xi", True)])
+        r, t, z, p, xi = ws["r"], ws["t"], ws["z"], ws["p"], ws["xi"]
+        xi.copy_(x)
+        torch.cuda.synchronize(self.device)
+        t0 = time.perf_counter()
+        S.dot(b, b, self.partials, scal, S.S_BNRM2, n=n)
+        self._allreduce_slot(S.S_BNRM2)
+        self._spmv_overlapped(xi, t)
+        torch.sub(b[:n], t, out=r)
+        # z0 = M^-1 r0, rz -> S_RR, true rr -> S_GAMMA;  p0 = z0
+        S.bjacobi_apply(minv, r, z, self.partials, scal, n, dof)
+        self._allreduce_slot(S.S_RR)
+        self._allreduce_slot(S.S_GAMMA)
+        p[:n] = z
+        res.bnrm2 = math.sqrt(max(self._host_scalar(S.S_BNRM2), 0.0))
+        rr = self._host_scalar(S.S_GAMMA)
+        res.r0nrm2 = math.sqrt(max(rr, 0.0))
+        rtol2 = max(res_atol, res_rtol * res.bnrm2) ** 2
+        converged = rtol2 > 0 and rr <= rtol2
+        ring = LaggedReadback(1, lag=2)
+
+        def check(j):
+            """Host test of the true rr after iteration j."""
+            nonlocal rr, converged
+            rr = float(ring.get(j)[0])
+            if not math.isfinite(rr):
+                raise FloatingPointError(
+                    f"block-jacobi PCG diverged: rr={rr} at it {j + 1}")
+            if rtol2 > 0 and rr <= rtol2:
+                converged = True
+                res.niterations = j + 1
+                return True
+            return False
+
+        k = 0
+        cur = torch.cuda.current_stream(self.device)
+        rr_slot = scal[S.S_GAMMA:S.S_GAMMA + 1]
+        while not converged and k < maxits:
+            if k >= ring.lag and check(k - ring.lag):
+                break
+            self._spmv_overlapped(p, t, fuse_dotslot=S.S_PT)
+            with self.prof.span("allreduce"):
+                self._allreduce_slot(S.S_PT)
+            # ONE fused kernel: alpha = rz/pt (device), r/x updates,
+            # z = M^-1 r, next rz (-> S_RR, rotated) and true rr (-> S_GAMMA)
+            with self.prof.span("update_bjacobi"):
+                S.bpcg_fused_update(r, xi, p, t, z, minv, scal,
+                                    self.partials, n, dof)
+            with self.prof.span("allreduce"):
+                self._allreduce_slot(S.S_RR)
+                self._allreduce_slot(S.S_GAMMA)
+            # p = (rz/rz_prev) p + z
+            with self.prof.span("daypx"):
+                S.daypx_ratio(p, z, scal, S.S_RR, S.S_RR_PREV, n=n)
+            ring.push(k, rr_slot, cur)
+            k += 1
+            res.niterations = k
+        if not converged:
+            for j in ring.tail(k):
+                if check(j):
+                    break
+        torch.cuda.synchronize(self.device)
+        res.tsolve = time.perf_counter() - t0
+        x.copy_(xi)
+        rr = self._host_scalar(S.S_GAMMA)
+        res.rnrm2 = math.sqrt(max(rr, 0.0))
+        res.converged = converged or (rtol2 > 0 and rr <= rtol2)
+        nnz_full = self.local.nnzA + self.local.nnzO
+        self._count_work(res, cg_flops_per_iter(nnz_full, n)
+                         + (2.0 * dof + 2.0) * n)
+        self._annotate_profile(res)
+        return res
+
     # -- pipelined CG -----------------------------------------------------
 
     def solve_pipelined(self, b: torch.Tensor, x: torch.Tensor, maxits: int = 100,

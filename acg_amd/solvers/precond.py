@@ -30,6 +30,59 @@ from ..part.subdomain import LocalSystem
 from ..utils.errors import AcgError, ErrCode
 
 
+BLOCK_DENSITY_MIN = 0.75  # the Block-SELL acceptance of CGSolverHIP
+
+
+def detect_block_dof(S: LocalSystem):
+    """The node size the GPU solver's format ladder would pick for matA:
+    the first of 4, 3, 2 at which Block-SELL is at least 0.75 dense, or
+    None when the matrix has no such block structure."""
+    from ..ops.torch_ref import bsell_from_csr
+
+    if S.nowned == 0:
+        return None
+    for dof in (4, 3, 2):
+        out = bsell_from_csr(S.A_rowptr, S.A_colidx, S.A_vals, dof)
+        if out is not None and out[3] >= BLOCK_DENSITY_MIN:
+            return dof
+    return None
+
+
+def block_jacobi_inverse(S: LocalSystem, dof: int) -> np.ndarray:
+    """Inverses of the dof x dof diagonal blocks of matA, (nnodes, dof, dof).
+    The block-Jacobi preconditioner M^-1 = blockdiag(A_ii)^-1 (beyond
+    reference; see jacobi_scale_system for aCG's PCNONE).  Every block must
+    be present and symmetric positive definite."""
+    n = S.nowned
+    if dof < 1 or n % dof:
+        raise AcgError(ErrCode.INVALID_VALUE,
+                       f"block Jacobi: {n} owned rows are not a multiple "
+                       f"of dof={dof}")
+    nnodes = n // dof
+    rows = np.repeat(np.arange(n, dtype=np.int64), np.diff(S.A_rowptr))
+    cols = np.asarray(S.A_colidx, dtype=np.int64)
+    m = (cols < n) & (rows // dof == cols // dof)
+    D = np.zeros((nnodes, dof, dof), dtype=np.float64)
+    np.add.at(D, (rows[m] // dof, rows[m] % dof, cols[m] % dof), S.A_vals[m])
+    have = np.zeros(nnodes, dtype=bool)
+    have[rows[m] // dof] = True
+    if not have.all():
+        raise AcgError(ErrCode.INVALID_VALUE,
+                       f"block Jacobi: {int((~have).sum())} nodes have no "
+                       f"diagonal block")
+    if nnodes == 0:
+        return D
+    try:
+        if not np.isfinite(D).all():
+            raise np.linalg.LinAlgError("non-finite block")
+        np.linalg.cholesky(D)
+    except np.linalg.LinAlgError:
+        raise AcgError(ErrCode.INVALID_VALUE,
+                       "block Jacobi needs symmetric positive definite "
+                       "diagonal blocks") from None
+    return np.linalg.inv(D)
+
+
 def jacobi_scale_system(S: LocalSystem, comm=None, device=None):
     """Return (S_scaled, s_owned): the symmetrically scaled system and the
     per-owned-row scale ``s = diag(A)^-1/2`` (``x = s * x_scaled`` maps

@@ -16,7 +16,7 @@ import numpy as np
 import torch
 
 from ..part.subdomain import HaloPattern
-from .stencil import _blocks, _slab_bounds
+from .stencil import _blocks, _slab_bounds, brick_order
 
 
 class DeviceSlabSystem:
@@ -293,4 +293,5 @@ def device_stencil_slab(gx: int, gy: int, gz: int, spec: dict,
         O_sell=(O_sellptr, O_cols, O_vals) if operator else None,
         mf_tables=mf_tables,
         _nnzA=nnzA, _nnzO=nnzO, halo=halo, device=device,
+        node_order=brick_order(gx, gy, gz) if nranks == 1 else None,
     )

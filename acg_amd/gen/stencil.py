@@ -137,6 +137,22 @@ def stencil_global(gx: int, gy: int, gz: int, spec: dict) -> SymCSRMatrix:
     return SymCSRMatrix.from_coo(n, i, j, v)
 
 
+def brick_order(gx: int, gy: int, gz: int,
+                brick: tuple[int, int, int] = (8, 8, 4)) -> np.ndarray:
+    """Node order that walks the grid brick by brick (x fastest inside a
+    brick and among bricks): ``order[new] = z*gx*gy + y*gx + x``.  The
+    ``node_order`` hint of a one-rank stencil system: 256 consecutive nodes
+    of this order share far more stencil pairs than 256 nodes of an x-line
+    order (see ops/symtile.py)."""
+    bx, by, bz = brick
+    z, y, x = np.meshgrid(np.arange(gz), np.arange(gy), np.arange(gx),
+                          indexing="ij")
+    nbx, nby = -(-gx // bx), -(-gy // by)
+    key = ((((z // bz) * nby + y // by) * nbx + x // bx) * bz + z % bz) * by
+    key = ((key + y % by) * bx + x % bx).ravel()
+    return np.argsort(key, kind="stable").astype(np.int64)
+
+
 def _slab_bounds(gz: int, rank: int, nranks: int) -> tuple[int, int]:
     z0 = (gz * rank) // nranks
     z1 = (gz * (rank + 1)) // nranks
@@ -328,4 +344,5 @@ def stencil_local_slab(gx: int, gy: int, gz: int, spec: dict,
         A_rowptr=A_rowptr, A_colidx=A_cols.astype(cdt), A_vals=A_vals,
         O_rowptr=O_rowptr, O_colidx=O_cols.astype(cdt), O_vals=O_vals,
         owned_global=owned_global, ghost_global=ghost_global, halo=halo,
+        node_order=brick_order(gx, gy, gz) if nranks == 1 else None,
     )

@@ -37,6 +37,7 @@ S_GAMMA_PREV = K.S_GAMMA_PREV
 S_ALPHA_PREV = K.S_ALPHA_PREV
 S_NSLOTS = K.S_NSLOTS
 MAXG = K.MAXG
+K_ST_TILE = 256  # nodes per BSELL-ST tile = one workgroup of k_spmv_bsell_st
 
 
 def _stream() -> int:
@@ -242,6 +243,33 @@ def spmv_bsell(bptr: torch.Tensor, bcol: torch.Tensor, bvals: torch.Tensor,
                  partials.data_ptr() if fuse else 0,
                  scal.data_ptr() if fuse else 0, dotslot, dot_accum, val32,
                  _stream())
+
+
+def spmv_bsell_st(st, x: torch.Tensor, y: torch.Tensor, *,
+                  partials: torch.Tensor | None = None,
+                  scal: torch.Tensor | None = None, dotslot: int = -1,
+                  dot_accum: bool = True, max_blocks: int = 0) -> int:
+    """Tile-symmetric Block-SELL SpMV; ``st`` from
+    :func:`acg_amd.ops.symtile.bsell_st_build`, ``x`` and ``y`` in its
+    permuted node order.  ``max_blocks`` > 0 caps the grid.  Returns the
+    number of blocks launched."""
+    if st.tile != K_ST_TILE:
+        raise ValueError(f"spmv_bsell_st: the kernel's tile is {K_ST_TILE} "
+                         f"nodes, this operator was built with {st.tile}")
+    n = st.nnodes * st.dof
+    if x.numel() < n or y.numel() < n:
+        raise ValueError("spmv_bsell_st: x and y must hold nnodes * dof values")
+    if x.dtype != torch.float64 or y.dtype != torch.float64:
+        raise TypeError("spmv_bsell_st: x and y must be float64")
+    fuse = scal is not None and dotslot >= 0
+    return K.spmv_bsell_st(st.ntiles, st.nslices, st.nnodes, st.dof, st.qmax,
+                           st.sptr.data_ptr(), st.spl.data_ptr(),
+                           st.scol.data_ptr(), st.sq.data_ptr(),
+                           st.svals.data_ptr(), st.nrecv.data_ptr(),
+                           x.data_ptr(), y.data_ptr(),
+                           partials.data_ptr() if fuse else 0,
+                           scal.data_ptr() if fuse else 0, dotslot, dot_accum,
+                           max_blocks, _stream())
 
 
 def stencil_spmv(mf, nrows_nodes: int, row0_node: int, x: torch.Tensor,

@@ -342,6 +342,116 @@ k_spmv_bsell(long nslices, long nnodes,
     }
 }
 
+// Tile-symmetric Block-SELL (BSELL-ST): a symmetric operator stores a block
+// pair (A_ij, A_ji = A_ij^T) ONCE when both nodes belong to the same
+// 256-node tile (= one workgroup).  The owner lane accumulates A x[c] for
+// itself and hands A^T x_self to the partner through LDS slot
+// lds[q][c - tile_base]; every (slot, node) cell has at most one writer
+// (builder invariant), and after one barrier each lane adds its nrecv
+// slots in slot order -- no LDS or global atomics, bitwise reproducible.
+// Layout per 64-node slice s (sptr in block units, values pair-major as
+// in BSELL): blocks j < spl[s] are plain for every lane; blocks
+// j >= spl[s] carry a byte sq (slot number, ST_NOSEND = plain or padding).
+// x and y are in the builder's permuted node order.  Occupancy is set by
+// LDS (qmax 8, dof 3: 48 KiB -> 3 workgroups per CU); unroll 2 keeps two
+// blocks' loads in flight per wave, unroll 4 (160 VGPRs) measured the same.
+#define ST_NOSEND 255
+
+template <int DOF, bool FUSE_DOT>
+__global__ void __launch_bounds__(BLOCK)
+k_spmv_bsell_st(long ntiles, long nslices, long nnodes,
+                const long* __restrict__ sptr,
+                const int* __restrict__ spl,
+                const int* __restrict__ scol,
+                const unsigned char* __restrict__ sq,
+                const double* __restrict__ svals,
+                const unsigned char* __restrict__ nrecv,
+                const double* __restrict__ x,
+                double* __restrict__ y,
+                double* __restrict__ partials) {
+    extern __shared__ double st_lds[];  // [qmax][DOF][BLOCK]
+    const int lane = threadIdx.x & (WAVE - 1);
+    const int wid = threadIdx.x >> 6;
+    double dacc = 0.0;
+    for (long t = blockIdx.x; t < ntiles; t += gridDim.x) {
+        const long tile_base = t * BLOCK;
+        const long s = t * (BLOCK / WAVE) + wid;
+        const long node = tile_base + threadIdx.x;
+        const bool live = s < nslices;  // wave-uniform
+        double acc[DOF];
+        #pragma unroll
+        for (int r = 0; r < DOF; ++r) acc[r] = 0.0;
+        if (live) {
+            const long nself = node < nnodes ? node : nnodes - 1;
+            double xs[DOF];
+            #pragma unroll
+            for (int r = 0; r < DOF; ++r) xs[r] = x[nself * DOF + r];
+            const long b0 = sptr[s];
+            const long blen = (sptr[s + 1] - b0) >> 6;
+            const long npl = spl[s];
+            const int* __restrict__ c = scol + b0 + lane;
+            const unsigned char* __restrict__ qp = sq + b0 + lane;
+            const double* __restrict__ v = svals + b0 * (DOF * DOF);
+            #pragma unroll 2
+            for (long j = 0; j < npl; ++j) {
+                const int cb = ld_nt(c + j * WAVE);
+                double xv[DOF];
+                #pragma unroll
+                for (int cc = 0; cc < DOF; ++cc) xv[cc] = x[(long)cb * DOF + cc];
+                const double* __restrict__ vj = v + j * (DOF * DOF) * WAVE;
+                #pragma unroll
+                for (int k = 0; k < DOF * DOF; ++k) {
+                    const double a = ld_nt(vj + bval_off<DOF * DOF>(k, lane));
+                    acc[k / DOF] += a * xv[k % DOF];
+                }
+            }
+            #pragma unroll 2
+            for (long j = npl; j < blen; ++j) {
+                const int cb = ld_nt(c + j * WAVE);
+                const int q = ld_nt(qp + j * WAVE);
+                double xv[DOF], tr[DOF];
+                #pragma unroll
+                for (int cc = 0; cc < DOF; ++cc) {
+                    xv[cc] = x[(long)cb * DOF + cc];
+                    tr[cc] = 0.0;
+                }
+                const double* __restrict__ vj = v + j * (DOF * DOF) * WAVE;
+                #pragma unroll
+                for (int k = 0; k < DOF * DOF; ++k) {
+                    const double a = ld_nt(vj + bval_off<DOF * DOF>(k, lane));
+                    acc[k / DOF] += a * xv[k % DOF];
+                    tr[k % DOF] += a * xs[k / DOF];
+                }
+                if (q != ST_NOSEND) {
+                    const int loc = (int)((long)cb - tile_base);
+                    #pragma unroll
+                    for (int cc = 0; cc < DOF; ++cc)
+                        st_lds[(q * DOF + cc) * BLOCK + loc] = tr[cc];
+                }
+            }
+        }
+        __syncthreads();
+        if (live && node < nnodes) {
+            const int nr = nrecv[node];
+            for (int q = 0; q < nr; ++q) {
+                #pragma unroll
+                for (int r = 0; r < DOF; ++r)
+                    acc[r] += st_lds[(q * DOF + r) * BLOCK + threadIdx.x];
+            }
+            #pragma unroll
+            for (int r = 0; r < DOF; ++r) {
+                y[node * DOF + r] = acc[r];
+                if (FUSE_DOT) dacc += x[node * DOF + r] * acc[r];
+            }
+        }
+        __syncthreads();  // the next trip rewrites the slots
+    }
+    if (FUSE_DOT) {
+        dacc = block_reduce(dacc);
+        if (threadIdx.x == 0) partials[blockIdx.x] = dacc;
+    }
+}
+
 // Classic-CG daypx folded into the BSELL SpMV (serial matA-only path):
 // instead of a separate p = beta p + r kernel (3n streams) the gather
 // computes beta*p_old[c] + r[c] on the fly and the row side materialises
@@ -1191,6 +1301,54 @@ void spmv_bsell(long nslices, long nnodes, int dof, uintptr_t bptr,
                            (int)blocks, (double*)scal, dotslot, dot_accum ? 1 : 0);
         check_hip("spmv_bsell_reduce");
     }
+}
+
+// Returns the number of blocks launched (= partials written when fused).
+// ``max_blocks`` > 0 caps the grid (grid-stride over tiles takes the rest).
+long spmv_bsell_st(long ntiles, long nslices, long nnodes, int dof, int qmax,
+                   uintptr_t sptr, uintptr_t spl, uintptr_t scol, uintptr_t sq,
+                   uintptr_t svals, uintptr_t nrecv, uintptr_t x, uintptr_t y,
+                   uintptr_t partials, uintptr_t scal, int dotslot,
+                   bool dot_accum, long max_blocks, uintptr_t stream) {
+    if (nnodes == 0 || ntiles == 0) return 0;
+    if (ntiles != (nslices + BLOCK / WAVE - 1) / (BLOCK / WAVE)
+        || nslices != (nnodes + WAVE - 1) / WAVE)
+        throw std::invalid_argument("spmv_bsell_st: tile/slice/node counts disagree");
+    if (qmax < 0 || qmax >= ST_NOSEND)
+        throw std::invalid_argument("spmv_bsell_st: qmax must be in [0, 255)");
+    const size_t lds = (size_t)qmax * dof * BLOCK * sizeof(double);
+    if (lds > 96 * 1024)
+        throw std::invalid_argument("spmv_bsell_st: qmax * dof needs more than 96 KiB of LDS");
+    long blocks = ntiles;
+    if (blocks > MAXG) blocks = MAXG;
+    if (max_blocks > 0 && blocks > max_blocks) blocks = max_blocks;
+    const bool fuse = partials != 0 && dotslot >= 0;
+    dim3 g((unsigned)blocks), b(BLOCK);
+    #define LST(D, FD) do { \
+        if (lds > 48 * 1024 && hipFuncSetAttribute( \
+                (const void*)k_spmv_bsell_st<D, FD>, \
+                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) \
+            throw std::runtime_error("spmv_bsell_st: cannot raise the LDS limit"); \
+        hipLaunchKernelGGL((k_spmv_bsell_st<D, FD>), g, b, lds, (hipStream_t)stream, \
+            ntiles, nslices, nnodes, (const long*)sptr, (const int*)spl, \
+            (const int*)scol, (const unsigned char*)sq, (const double*)svals, \
+            (const unsigned char*)nrecv, (const double*)x, (double*)y, \
+            (double*)partials); } while (0)
+    switch (dof) {
+        case 2: if (fuse) { LST(2, true); } else { LST(2, false); } break;
+        case 3: if (fuse) { LST(3, true); } else { LST(3, false); } break;
+        case 4: if (fuse) { LST(4, true); } else { LST(4, false); } break;
+        default: throw std::runtime_error("spmv_bsell_st: dof must be 2/3/4");
+    }
+    #undef LST
+    check_hip("spmv_bsell_st");
+    if (fuse) {
+        hipLaunchKernelGGL(k_reduce_partials, dim3(1), dim3(BLOCK), 0,
+                           (hipStream_t)stream, (const double*)partials,
+                           (int)blocks, (double*)scal, dotslot, dot_accum ? 1 : 0);
+        check_hip("spmv_bsell_st_reduce");
+    }
+    return blocks;
 }
 
 void spmv_bsell_daypx(long nslices, long nnodes, int dof, uintptr_t bptr,
@@ -3347,6 +3505,8 @@ PYBIND11_MODULE(_acg_kernels, m) {
     m.def("stencil_fill", &stencil_fill);
     m.def("spmv_bsell", &spmv_bsell);
     m.def("spmv_bsell_daypx", &spmv_bsell_daypx);
+    m.def("spmv_bsell_st", &spmv_bsell_st);
+    m.attr("ST_NOSEND") = ST_NOSEND;
     m.def("stencil_blocklen", &stencil_blocklen);
     m.def("stencil_bfill", &stencil_bfill);
     m.def("stencil_spmv", &stencil_spmv);

@@ -397,6 +397,37 @@ def spmv_bsell_daypx(bptr, bcol, bvals, nnodes: int, dof: int, pold, rvec,
     scal[dotslot] = torch.dot(pn, contrib)
 
 
+def spmv_bsell_st(st, x, y, *, partials=None, scal=None, dotslot: int = -1,
+                  dot_accum: bool = True, max_blocks: int = 0) -> None:
+    """y = A x on a BSELL-ST operator (ops/symtile.py), x and y in its
+    permuted node order.  Follows k_spmv_bsell_st: own products first, the
+    owner's A^T x_self lands in slot q of the partner, each node then adds
+    its nrecv slots in slot order."""
+    from .symtile import NOSEND, decode_st
+
+    nn, dof = st.nnodes, st.dof
+    n = nn * dof
+    node, col, vals, q = decode_st(st)
+    live = node < nn
+    node, col, vals, q = node[live], col[live], vals[live], q[live]
+    A = vals.view(-1, dof, dof)
+    xb = x[:n].view(nn, dof)
+    contrib = torch.zeros(nn, dof, dtype=torch.float64, device=x.device)
+    contrib.index_add_(0, node, torch.einsum("brc,bc->br", A, xb[col]))
+    snd = q != NOSEND
+    slots = torch.zeros(max(st.qmax, 1), nn, dof, dtype=torch.float64,
+                        device=x.device)
+    slots[q[snd], col[snd]] = torch.einsum("brc,br->bc", A[snd], xb[node[snd]])
+    nr = st.nrecv[:nn].long()
+    for s in range(st.qmax):
+        contrib += torch.where((nr > s)[:, None], slots[s], 0.0)
+    contrib = contrib.reshape(-1)
+    y[:n] = contrib
+    if scal is not None and dotslot >= 0:
+        d = torch.dot(x[:n], contrib)
+        scal[dotslot] = scal[dotslot] + d if dot_accum else d
+
+
 def cg_prep_pt(scal) -> None:
     scal[S_PT] = 0.0
 

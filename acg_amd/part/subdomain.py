@@ -92,6 +92,9 @@ class LocalSystem:
     owned_global: np.ndarray  # global row id of local row i (i < nowned)
     ghost_global: np.ndarray
     halo: HaloPattern
+    # optional hint for tile-local formats (BSELL-ST): node_order[new] = old
+    # node, an order in which consecutive nodes are graph neighbours
+    node_order: np.ndarray | None = None
 
     @property
     def nlocal(self) -> int:

@@ -39,6 +39,12 @@ from .base import (ColumnTolerances, SolveResult, block_results,
                    refine, solve_multi_by_column)
 
 
+# Whether a solver builds BSELL-ST without being asked (force_format or
+# ACG_BSELL_ST=1); set from the interleaved measurement in
+# profiles/symtile.md.
+BSELL_ST_DEFAULT = True
+
+
 class LaggedReadback:
     """Ring of ``lag + 1`` pinned host buffers (``width`` doubles each) and
     events for the lagged host convergence test: iteration k pushes its
@@ -109,6 +115,9 @@ class CGSolverHIP:
         self.O_rowptr = self.O_colidx = self.O_vals = None
         self.lanesA = self.lanesO = lanes or 16
         self.bsell = None
+        # tile-symmetric BSELL (ops/symtile.py) of the same operator; only
+        # the serial classic solve runs on it, everything else on bsell
+        self.bsell_st = None
         self.hybrid = None  # (rowlist int32, bins) row-binned CSR
         # matrix-free analytic operator (dof=1 stencils, opt-in): the SpMV
         # reads NO matrix data -- see ops/kernels.hip k_stencil_spmv.
@@ -157,6 +166,7 @@ class CGSolverHIP:
         self.megafuse_auto = (self.can_megafuse
                               and (self.matfree is not None
                                    or L.nnzA / max(L.nowned, 1) <= 16.0))
+        self._build_symtile(force_format)
         self.halo = HaloExchange(L.halo, L.nowned, self.device, comm)
         self.scal = ops.alloc_scalars(self.device)
         self.partials = ops.alloc_partials(self.device)
@@ -281,9 +291,9 @@ class CGSolverHIP:
             mk_sell(1)
         elif force == "sigma":
             mk_sell(4096)
-        elif force == "bsell":
+        elif force in ("bsell", "bsell-st"):
             if not mk_bsell():
-                raise ValueError("force_format=bsell: no dense dof x dof "
+                raise ValueError(f"force_format={force}: no dense dof x dof "
                                  "block structure (density < 0.75)")
         elif use_sell:  # auto ladder
             waste = mk_sell(1)
@@ -296,6 +306,36 @@ class CGSolverHIP:
             mk_bsell()
         if self.sell is not None or self.bsell is not None:
             self.A_rowptr = self.A_colidx = self.A_vals = None  # free CSR
+
+    def _build_symtile(self, force: str | None) -> None:
+        """Build BSELL-ST next to BSELL where the classic solve can use it:
+        one rank, no matO, a bsell operator, no other format forced.  The
+        builder's own gate (exact transposes inside a tile, padded bytes
+        <= 0.9 of BSELL's) decides; a refusal keeps BSELL, except under
+        ``force_format="bsell-st"``, which raises.  Without the force the
+        format is built when BSELL_ST_DEFAULT or ACG_BSELL_ST=1 says so;
+        ACG_BSELL_ST=0 is the kill switch."""
+        from ..ops.symtile import bsell_st_build
+
+        env = os.environ.get("ACG_BSELL_ST", "")
+        serial = self.comm is None or self.comm.size == 1
+        wanted = force == "bsell-st" or (
+            force is None and (env == "1" or (BSELL_ST_DEFAULT and env != "0")))
+        if (wanted and env != "0" and serial and self.local.nnzO == 0
+                and self.bsell is not None and self.matfree is None):
+            bptr, bcol, bvals, dof = self.bsell
+            self.bsell_st = bsell_st_build(
+                bptr, bcol, bvals, self.n // dof, dof,
+                getattr(self.local, "node_order", None))
+            if self.bsell_st is not None:
+                print(f"# classic CG operator format: bsell-st "
+                      f"({self.bsell_st.ratio:.3f} of the bsell bytes)",
+                      file=sys.stderr, flush=True)
+        if force == "bsell-st" and self.bsell_st is None:
+            raise ValueError(
+                "force_format=bsell-st: not built (needs one rank, no matO, "
+                "ACG_BSELL_ST != 0, exact transposes inside every tile and "
+                "stored bytes <= 0.9 of BSELL's)")
 
     def _workspace(self, key: str, names) -> dict:
         """Per-method persistent vectors, base-address STAGGERED: equal-size
@@ -402,12 +442,18 @@ class CGSolverHIP:
         if hasattr(self.local, "A_sell"):
             return "device-generated"
         if self.bsell is not None:
-            return "bsell"
+            return "bsell"  # classic_format says whether solve() takes bsell-st
         if self.sell is not None:
             return "sigma" if self.sell_perm is not None else "sell"
         if self.hybrid is not None:
             return "hybrid" if self.hybrid["sellptr"] is not None else "binned"
         return "csr"
+
+    @property
+    def classic_format(self) -> str:
+        """Operator format of the plain classic solve: "bsell-st" when the
+        tile-symmetric operator was built, else :meth:`_format_name`."""
+        return "bsell-st" if self.bsell_st is not None else self._format_name()
 
     def _lowprec_values(self) -> torch.Tensor:
         """fp32 copy of the matA values of the chosen format (plain SELL,
@@ -569,15 +615,39 @@ class CGSolverHIP:
         ws = self._workspace("classic", [("r", False), ("t", False),
                                          ("p", True), ("xi", True)])
         r, t, p, xi = ws["r"], ws["t"], ws["p"], ws["xi"]
-        xi.copy_(x)
+        # BSELL-ST: the whole solve runs in the operator's permuted node
+        # order (b and x gathered once here, x scattered back in
+        # _finish_classic); the vector kernels do not care about the order
+        st = self.bsell_st
+        if lowprec or fold_daypx is True or diff_atol > 0 or diff_rtol > 0:
+            st = None
+
+        def spmv(xv, yv, fuse_dotslot=-1):
+            if st is None:
+                self._spmv_overlapped(xv, yv, fuse_dotslot=fuse_dotslot,
+                                      lowprec=lowprec)
+                return
+            with self.prof.span("spmvA"):
+                S.spmv_bsell_st(st, xv, yv, partials=self.partials,
+                                scal=scal if fuse_dotslot >= 0 else None,
+                                dotslot=fuse_dotslot, dot_accum=False)
+
+        if st is None:
+            xi.copy_(x)
+        else:
+            torch.index_select(x[:n], 0, st.vperm, out=xi[:n])
         torch.cuda.synchronize(self.device)
         t0 = time.perf_counter()
         # bnrm2
         S.dot(b, b, self.partials, scal, S.S_BNRM2, n=n)
         self._allreduce_slot(S.S_BNRM2)
         # r0 = b - A x0;  p = r0
-        self._spmv_overlapped(xi, t, lowprec=lowprec)
-        torch.sub(b[:n], t, out=r)
+        spmv(xi, t)
+        if st is None:
+            torch.sub(b[:n], t, out=r)
+        else:
+            torch.index_select(b[:n], 0, st.vperm, out=r)
+            r.sub_(t)
         p[:n] = r
         S.dot(r, r, self.partials, scal, S.S_RR, n=n)
         self._allreduce_slot(S.S_RR)
@@ -641,7 +711,7 @@ class CGSolverHIP:
                 return
             # halo+split SpMV with the (p,t) reduction fused into both
             # passes (matA overwrites the slot, matO accumulates)
-            self._spmv_overlapped(p, t, fuse_dotslot=S.S_PT, lowprec=lowprec)
+            spmv(p, t, fuse_dotslot=S.S_PT)
             with self.prof.span("allreduce"):
                 self._allreduce_slot(S.S_PT)
             # fused r/x update (alpha = rr/pt on device) + combined
@@ -701,7 +771,7 @@ class CGSolverHIP:
             for j in ring.tail(maxits):
                 if check(j):
                     break
-        return self._finish_classic(res, x, xi, converged, rtol2, t0)
+        return self._finish_classic(res, x, xi, converged, rtol2, t0, st)
 
     def _solve_diffmode(self, res, r, t, p, xi, rtol2: float, dtol: float,
                         maxits: int) -> bool:
@@ -738,11 +808,16 @@ class CGSolverHIP:
         return converged
 
     def _finish_classic(self, res, x, xi, converged: bool, rtol2: float,
-                        t0: float):
+                        t0: float, st=None):
+        """``st``: the BSELL-ST operator the solve ran on; xi is then in
+        its node order and goes back to the caller's."""
         S = ops
         torch.cuda.synchronize(self.device)
         res.tsolve = time.perf_counter() - t0
-        x.copy_(xi)
+        if st is None:
+            x.copy_(xi)
+        else:
+            x[:self.n].index_copy_(0, st.vperm, xi[:self.n])
         rr = self._host_scalar(S.S_RR)
         res.rnrm2 = math.sqrt(max(rr, 0.0))
         res.converged = converged or (rtol2 > 0 and rr <= rtol2)

@@ -68,6 +68,11 @@ def make_parser() -> argparse.ArgumentParser:
                    help="acg-mixed / cpu-mixed: relative residual reduction "
                         "of each fp32-operator sweep between fp64 "
                         "refinement steps (default: the solver's)")
+    p.add_argument("--residual-replacement", type=int, default=0, metavar="N",
+                   help="acg-pipelined / cpu-pipelined: every N iterations "
+                        "recompute r = b - A x, w = A r, t = A p, z = A t "
+                        "instead of trusting the recurrences (0 = off; "
+                        "beyond reference)")
     p.add_argument("--epsilon", type=float, default=0.0,
                    help="diagonal shift added to A")
     p.add_argument("--warmup", type=int, default=10,
@@ -165,6 +170,19 @@ def _check_multi_rhs(k: int, solver_name: str, args) -> None:
                        "several right-hand sides")
 
 
+RR_SOLVERS = ("acg-pipelined", "cpu-pipelined")
+
+
+def _check_residual_replacement(period: int, solver_name: str) -> None:
+    if period < 0:
+        raise AcgError(ErrCode.INVALID_VALUE,
+                       "--residual-replacement must not be negative")
+    if period and solver_name not in RR_SOLVERS:
+        raise AcgError(ErrCode.NOT_SUPPORTED,
+                       f"--residual-replacement is not supported by "
+                       f"{solver_name} (use acg-pipelined or cpu-pipelined)")
+
+
 def main(argv=None) -> int:
     args = make_parser().parse_args(argv)
     import torch
@@ -185,6 +203,7 @@ def main(argv=None) -> int:
     if args.nrhs < 1:
         raise AcgError(ErrCode.INVALID_VALUE, "--nrhs must be at least 1")
     _check_multi_rhs(args.nrhs, solver_name, args)
+    _check_residual_replacement(args.residual_replacement, solver_name)
     if gpu_solver and not has_gpu:
         print("error: GPU solver requested but no GPU is available", file=sys.stderr)
         return 1
@@ -409,7 +428,8 @@ def main(argv=None) -> int:
             elif args.warmup:
                 if solver_name == "acg-pipelined":
                     solver.solve_pipelined(b, x.clone(), maxits=args.warmup,
-                                           res_rtol=0.0)
+                                           res_rtol=0.0,
+                                           rr_period=args.residual_replacement)
                 elif solver_name == "acg-jacobi":
                     solver.solve_jacobi(b, x.clone(), maxits=args.warmup,
                                         res_rtol=0.0)
@@ -431,7 +451,8 @@ def main(argv=None) -> int:
             elif solver_name == "acg-pipelined":
                 res = solver.solve_pipelined(b, x, maxits=args.max_iterations,
                                              res_atol=args.residual_atol,
-                                             res_rtol=args.residual_rtol)
+                                             res_rtol=args.residual_rtol,
+                                             rr_period=args.residual_replacement)
             elif solver_name == "acg-jacobi":
                 res = solver.solve_jacobi(b, x, maxits=args.max_iterations,
                                           res_atol=args.residual_atol,
@@ -467,7 +488,8 @@ def main(argv=None) -> int:
             elif solver_name == "cpu-pipelined":
                 res = solver.solve_pipelined(b, x, maxits=args.max_iterations,
                                              res_atol=args.residual_atol,
-                                             res_rtol=args.residual_rtol)
+                                             res_rtol=args.residual_rtol,
+                                             rr_period=args.residual_replacement)
             elif solver_name == "cpu-jacobi":
                 res = solver.solve_jacobi(b, x, maxits=args.max_iterations,
                                           res_atol=args.residual_atol,
@@ -508,6 +530,11 @@ def main(argv=None) -> int:
                 and rc.block_breakdown >= 0):
             print(f"block CG handed over to the per-column iteration at "
                   f"block iteration {rc.block_breakdown}", file=sys.stderr)
+        if (args.verbose and rank == 0 and rc is not None
+                and args.residual_replacement):
+            print(f"residual replacement every {args.residual_replacement} "
+                  f"iterations: {rc.nreplacements} replacements",
+                  file=sys.stderr)
 
     # true-residual integrity check: ||b - A x|| of the returned iterate,
     # independent of the solver's residual recursion (bench.py computes the

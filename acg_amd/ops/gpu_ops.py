@@ -245,6 +245,153 @@ def spmv_bsell(bptr: torch.Tensor, bcol: torch.Tensor, bvals: torch.Tensor,
                  _stream())
 
 
+def _spmv2_check(what: str, vals: torch.Tensor, nrows: int, ncols: int,
+                 x1, x2, y1, y2, b, partials) -> None:
+    """Argument checks shared by the dual SpMV wrappers, all before any
+    launch: fp64 operator values only, fp64 contiguous vectors on the
+    operator's GPU, gathered vectors ``ncols`` long (owned rows plus the
+    ghost tail), outputs and ``b`` ``nrows`` long, no two of
+    y1/y2/x1/x2/b sharing memory."""
+    if vals.dtype != torch.float64:
+        raise TypeError(f"{what}: operator values must be float64, got "
+                        f"{vals.dtype} (no dual kernel for fp32-stored values)")
+    if ncols < nrows:
+        raise ValueError(f"{what}: ncols={ncols} is less than nrows={nrows}")
+    vecs = [("x1", x1, ncols), ("x2", x2, ncols), ("y1", y1, nrows),
+            ("y2", y2, nrows)]
+    if b is not None:
+        vecs.append(("b", b, nrows))
+    for nm, v, need in vecs:
+        if v.dtype != torch.float64:
+            raise TypeError(f"{what}: {nm} must be float64, got {v.dtype}")
+        if v.dim() != 1 or not v.is_contiguous() or v.numel() < need:
+            raise ValueError(f"{what}: {nm} must be a contiguous vector of at "
+                             f"least {need} entries, got {tuple(v.shape)}")
+        if v.device != vals.device:
+            raise ValueError(f"{what}: {nm} lives on {v.device}, the operator "
+                             f"on {vals.device}")
+    spans = [(nm, v.data_ptr(), v.data_ptr() + 8 * v.numel()) for nm, v, _ in vecs]
+    for i, (na, a0, a1) in enumerate(spans):
+        for nb_, b0, b1 in spans[i + 1:]:
+            if a0 < b1 and b0 < a1:
+                raise ValueError(f"{what}: {na} and {nb_} share memory")
+    if partials is not None and (
+            partials.dtype != torch.float64 or not partials.is_contiguous()
+            or partials.numel() < 2 * MAXG or partials.device != vals.device):
+        raise ValueError(f"{what}: partials must be contiguous float64 with "
+                         f"{2 * MAXG} entries on {vals.device}")
+
+
+def spmv2_sell(sellptr: torch.Tensor, cols: torch.Tensor, vals: torch.Tensor,
+               nrows: int, x1: torch.Tensor, x2: torch.Tensor,
+               y1: torch.Tensor, y2: torch.Tensor, *, ncols: int,
+               b: torch.Tensor | None = None,
+               partials: torch.Tensor | None = None,
+               perm: torch.Tensor | None = None) -> int:
+    """Dual SELL-C-64(-sigma) SpMV, one pass over the matrix:
+    ``y1 = A x1`` (``b - A x1`` when ``b`` is given) and ``y2 = A x2``.
+    ``ncols`` is the length the gathered vectors need (owned rows plus
+    ghosts).  With ``partials`` the block partials of (x1,x1) and (y1,x1)
+    land in ``partials[:nb]`` and ``partials[MAXG:MAXG + nb]`` for
+    :func:`pipelined_replace_finalize`; returns nb, the blocks launched."""
+    _spmv2_check("spmv2_sell", vals, nrows, ncols, x1, x2, y1, y2, b, partials)
+    if cols.dtype not in (torch.int32, torch.int64):
+        raise TypeError(f"spmv2_sell: cols must be int32 or int64, got {cols.dtype}")
+    if perm is not None and perm.dtype != torch.int32:
+        raise TypeError("spmv2_sell: perm must be int32")
+    nslices = sellptr.numel() - 1
+    if nslices <= 0 or nrows <= 0:
+        return 0
+    if nslices != (nrows + 63) // 64:
+        raise ValueError(f"spmv2_sell: {nslices} slices do not hold {nrows} rows")
+    if perm is not None and perm.numel() < nslices * 64:
+        raise ValueError(f"spmv2_sell: perm has {perm.numel()} entries, "
+                         f"needs {nslices * 64}")
+    if cols.numel() != vals.numel():
+        raise ValueError(f"spmv2_sell: cols and vals differ in length: "
+                         f"{cols.numel()} vs {vals.numel()}")
+    return int(K.spmv2_sell(
+        nslices, nrows, sellptr.data_ptr(), cols.data_ptr(),
+        1 if cols.dtype == torch.int64 else 0, vals.data_ptr(),
+        x1.data_ptr(), x2.data_ptr(), b.data_ptr() if b is not None else 0,
+        y1.data_ptr(), y2.data_ptr(),
+        partials.data_ptr() if partials is not None else 0,
+        perm.data_ptr() if perm is not None else 0, _stream()))
+
+
+def spmv2_bsell(bptr: torch.Tensor, bcol: torch.Tensor, bvals: torch.Tensor,
+                nnodes: int, dof: int, x1: torch.Tensor, x2: torch.Tensor,
+                y1: torch.Tensor, y2: torch.Tensor, *, ncols: int,
+                b: torch.Tensor | None = None,
+                partials: torch.Tensor | None = None) -> int:
+    """Dual Block-SELL SpMV (dof 2/3/4); see :func:`spmv2_sell`."""
+    if dof not in (2, 3, 4):
+        raise ValueError(f"spmv2_bsell: dof must be 2, 3 or 4, got {dof}")
+    _spmv2_check("spmv2_bsell", bvals, nnodes * dof, ncols, x1, x2, y1, y2, b,
+                 partials)
+    if bcol.dtype != torch.int32:
+        raise TypeError(f"spmv2_bsell: bcol must be int32, got {bcol.dtype}")
+    nslices = bptr.numel() - 1
+    if nslices <= 0 or nnodes <= 0:
+        return 0
+    if nslices != (nnodes + 63) // 64:
+        raise ValueError(f"spmv2_bsell: {nslices} slices do not hold {nnodes} nodes")
+    if bvals.numel() != bcol.numel() * dof * dof:
+        raise ValueError(f"spmv2_bsell: {bcol.numel()} block columns do not "
+                         f"match {bvals.numel()} values of dof {dof}")
+    return int(K.spmv2_bsell(
+        nslices, nnodes, dof, bptr.data_ptr(), bcol.data_ptr(),
+        bvals.data_ptr(), x1.data_ptr(), x2.data_ptr(),
+        b.data_ptr() if b is not None else 0, y1.data_ptr(), y2.data_ptr(),
+        partials.data_ptr() if partials is not None else 0, _stream()))
+
+
+def dot2_slices(r: torch.Tensor, w: torch.Tensor, nunits: int, dof: int,
+                partials: torch.Tensor, *,
+                perm: torch.Tensor | None = None) -> int:
+    """Block partials of (r,r) and (w,r) over ``nunits * dof`` rows in the
+    row order and block partition of the fused dual SpMV (dof 1: SELL rows,
+    optional sigma ``perm``; dof 2/3/4: BSELL nodes), for
+    :func:`pipelined_replace_finalize`.  Returns the blocks launched."""
+    what = "dot2_slices"
+    if dof not in (1, 2, 3, 4) or (perm is not None and dof != 1):
+        raise ValueError(f"{what}: dof must be 1..4 (perm only with dof 1), "
+                         f"got dof={dof}")
+    n = nunits * dof
+    for nm, v in (("r", r), ("w", w)):
+        if v.dtype != torch.float64:
+            raise TypeError(f"{what}: {nm} must be float64, got {v.dtype}")
+        if v.dim() != 1 or not v.is_contiguous() or v.numel() < n:
+            raise ValueError(f"{what}: {nm} must be a contiguous vector of at "
+                             f"least {n} entries, got {tuple(v.shape)}")
+    if (partials.dtype != torch.float64 or not partials.is_contiguous()
+            or partials.numel() < 2 * MAXG):
+        raise ValueError(f"{what}: partials must be contiguous float64 with "
+                         f"{2 * MAXG} entries")
+    nslices = (nunits + 63) // 64
+    if perm is not None and (perm.dtype != torch.int32
+                             or perm.numel() < nslices * 64):
+        raise ValueError(f"{what}: perm must be int32 with {nslices * 64} entries")
+    if nunits <= 0:
+        return 0
+    return int(K.dot2_slices(nslices, nunits, dof, r.data_ptr(), w.data_ptr(),
+                             perm.data_ptr() if perm is not None else 0,
+                             partials.data_ptr(), _stream()))
+
+
+def pipelined_replace_finalize(partials: torch.Tensor, nblocks: int,
+                               scal: torch.Tensor) -> None:
+    """scal[GAMMA], scal[DELTA] = sums of the two partial halves of a fused
+    dual SpMV.  No other slot is written (GAMMA_PREV / ALPHA_PREV keep the
+    rotation of the iteration just finished)."""
+    what = "pipelined_replace_finalize"
+    if not 0 <= nblocks <= MAXG:
+        raise ValueError(f"{what}: nblocks must be in 0..{MAXG}, got {nblocks}")
+    _bj_slab(what, scal, partials, scal.device)
+    K.pipelined_replace_finalize(partials.data_ptr(), nblocks, scal.data_ptr(),
+                                 _stream())
+
+
 def spmv_bsell_st(st, x: torch.Tensor, y: torch.Tensor, *,
                   partials: torch.Tensor | None = None,
                   scal: torch.Tensor | None = None, dotslot: int = -1,

@@ -342,6 +342,179 @@ k_spmv_bsell(long nslices, long nnodes,
     }
 }
 
+// ---------------------------------------------------------------------------
+// Dual SpMV: the operator applied to TWO separate fp64 vectors in one pass
+// over the matrix (residual replacement of the pipelined CG: (b - A x, A p),
+// then (A r, A t)).  Same layouts, slice-per-wave mapping, non-temporal
+// matrix/index loads and padding conventions as k_spmv_sell / k_spmv_bsell;
+// every value and index is loaded once and feeds two gathers.
+//   y1 = RESID ? b - A x1 : A x1,   y2 = A x2
+// FUSE_DOT: per-block partials of (x1,x1) and (y1,x1) over the owned rows in
+// the two-half layout of k_pipelined_fused (partials[blk], partials[MAXG+blk]).
+// Both columns run the same sequence of fp operations, so x1 == x2 gives
+// bitwise y1 == y2 without RESID.  Unroll 4 keeps 8 gathers in flight per
+// lane, the same as the single-vector kernel's unroll 8.
+__device__ __forceinline__ void spmv2_dots(double g, double d, double* partials) {
+    g = block_reduce(g);
+    __syncthreads();
+    d = block_reduce(d);
+    if (threadIdx.x == 0) {
+        partials[blockIdx.x] = g;
+        partials[MAXG + blockIdx.x] = d;
+    }
+}
+
+template <typename ColT, bool RESID, bool FUSE_DOT, bool PERM>
+__global__ void __launch_bounds__(BLOCK)
+k_spmv2_sell(long nslices, long nrows,
+             const long* __restrict__ sellptr,
+             const ColT* __restrict__ cols,
+             const double* __restrict__ vals,
+             const double* __restrict__ x1,
+             const double* __restrict__ x2,
+             const double* __restrict__ b,
+             double* __restrict__ y1,
+             double* __restrict__ y2,
+             double* __restrict__ partials,
+             const int* __restrict__ perm) {
+    constexpr int UNROLL = 4;
+    const int lane = threadIdx.x & (WAVE - 1);
+    const long wslice = ((long)blockIdx.x * BLOCK + threadIdx.x) >> 6;
+    const long nw = ((long)gridDim.x * BLOCK) >> 6;
+    double g = 0.0, d = 0.0;
+    for (long s = wslice; s < nslices; s += nw) {
+        const long base = sellptr[s];
+        const long len = (sellptr[s + 1] - base) >> 6;  // entries per row
+        const double* __restrict__ v = vals + base + lane;
+        const ColT* __restrict__ c = cols + base + lane;
+        double sum1 = 0.0, sum2 = 0.0;
+        long j = 0;
+        for (; j + UNROLL <= len; j += UNROLL) {
+            double a[UNROLL], xa[UNROLL], xb[UNROLL];
+            #pragma unroll
+            for (int u = 0; u < UNROLL; ++u) {
+                a[u] = ld_nt(v + (j + u) * WAVE);
+                const ColT ci = ld_nt(c + (j + u) * WAVE);
+                xa[u] = x1[ci];
+                xb[u] = x2[ci];
+            }
+            #pragma unroll
+            for (int u = 0; u < UNROLL; ++u) {
+                sum1 += a[u] * xa[u];
+                sum2 += a[u] * xb[u];
+            }
+        }
+        for (; j < len; ++j) {
+            const double a = ld_nt(v + j * WAVE);
+            const ColT ci = ld_nt(c + j * WAVE);
+            sum1 += a * x1[ci];
+            sum2 += a * x2[ci];
+        }
+        const long row = PERM ? (long)perm[s * WAVE + lane] : s * WAVE + lane;
+        if (row < nrows) {
+            const double o1 = RESID ? b[row] - sum1 : sum1;
+            y1[row] = o1;
+            y2[row] = sum2;
+            if (FUSE_DOT) {
+                const double xr = x1[row];
+                g += xr * xr;
+                d += o1 * xr;
+            }
+        }
+    }
+    if (FUSE_DOT) spmv2_dots(g, d, partials);
+}
+
+template <int DOF, bool RESID, bool FUSE_DOT>
+__global__ void __launch_bounds__(BLOCK)
+k_spmv2_bsell(long nslices, long nnodes,
+              const long* __restrict__ bptr,
+              const int* __restrict__ bcol,
+              const double* __restrict__ bvals,
+              const double* __restrict__ x1,
+              const double* __restrict__ x2,
+              const double* __restrict__ b,
+              double* __restrict__ y1,
+              double* __restrict__ y2,
+              double* __restrict__ partials) {
+    const int lane = threadIdx.x & (WAVE - 1);
+    const long wslice = ((long)blockIdx.x * BLOCK + threadIdx.x) >> 6;
+    const long nw = ((long)gridDim.x * BLOCK) >> 6;
+    double g = 0.0, d = 0.0;
+    for (long s = wslice; s < nslices; s += nw) {
+        const long b0 = bptr[s];
+        const long blen = (bptr[s + 1] - b0) >> 6;  // blocks per node
+        const int* __restrict__ c = bcol + b0 + lane;
+        const double* __restrict__ v = bvals + b0 * (DOF * DOF);
+        double acc1[DOF], acc2[DOF];
+        #pragma unroll
+        for (int r = 0; r < DOF; ++r) { acc1[r] = 0.0; acc2[r] = 0.0; }
+        for (long j = 0; j < blen; ++j) {
+            const int cb = ld_nt(c + j * WAVE);
+            double xa[DOF], xb[DOF];
+            #pragma unroll
+            for (int cc = 0; cc < DOF; ++cc) {
+                xa[cc] = x1[(long)cb * DOF + cc];
+                xb[cc] = x2[(long)cb * DOF + cc];
+            }
+            const double* __restrict__ vj = v + j * (DOF * DOF) * WAVE;
+            #pragma unroll
+            for (int k = 0; k < DOF * DOF; ++k) {
+                const double a = ld_nt(vj + bval_off<DOF * DOF>(k, lane));
+                acc1[k / DOF] += a * xa[k % DOF];
+                acc2[k / DOF] += a * xb[k % DOF];
+            }
+        }
+        const long node = s * WAVE + lane;
+        if (node < nnodes) {
+            #pragma unroll
+            for (int r = 0; r < DOF; ++r) {
+                const long row = node * DOF + r;
+                const double o1 = RESID ? b[row] - acc1[r] : acc1[r];
+                y1[row] = o1;
+                y2[row] = acc2[r];
+                if (FUSE_DOT) {
+                    const double xr = x1[row];
+                    g += xr * xr;
+                    d += o1 * xr;
+                }
+            }
+        }
+    }
+    if (FUSE_DOT) spmv2_dots(g, d, partials);
+}
+
+// (r,r) and (w,r) partials in exactly the row order and block partition of
+// the fused dual SpMV (lane = SELL row or BSELL node, DOF rows in turn, one
+// partial pair per block).  The four-SpMV replacement uses it where the dual
+// kernels could run, so switching between the two paths changes the number
+// of matrix passes and not one bit of gamma / delta.
+template <int DOF, bool PERM>
+__global__ void __launch_bounds__(BLOCK)
+k_dot2_slices(long nslices, long nunits,
+              const double* __restrict__ r,
+              const double* __restrict__ w,
+              const int* __restrict__ perm,
+              double* __restrict__ partials) {
+    const int lane = threadIdx.x & (WAVE - 1);
+    const long wslice = ((long)blockIdx.x * BLOCK + threadIdx.x) >> 6;
+    const long nw = ((long)gridDim.x * BLOCK) >> 6;
+    double g = 0.0, d = 0.0;
+    for (long s = wslice; s < nslices; s += nw) {
+        const long unit = PERM ? (long)perm[s * WAVE + lane] : s * WAVE + lane;
+        if (unit < nunits) {
+            #pragma unroll
+            for (int k = 0; k < DOF; ++k) {
+                const double xr = r[unit * DOF + k];
+                const double o1 = w[unit * DOF + k];
+                g += xr * xr;
+                d += o1 * xr;
+            }
+        }
+    }
+    spmv2_dots(g, d, partials);
+}
+
 // Tile-symmetric Block-SELL (BSELL-ST): a symmetric operator stores a block
 // pair (A_ij, A_ji = A_ij^T) ONCE when both nodes belong to the same
 // 256-node tile (= one workgroup).  The owner lane accumulates A x[c] for
@@ -1132,6 +1305,27 @@ k_pipelined_finalize(const double* __restrict__ partials, int nblocks,
         pipelined_coeffs(scal, first, &beta, &alpha);
         scal[S_GAMMA_PREV] = scal[S_GAMMA];
         scal[S_ALPHA_PREV] = alpha;
+        scal[S_GAMMA] = g;
+        scal[S_DELTA] = d;
+    }
+}
+
+// Finalize of a residual replacement: gamma = (r,r) and delta = (w,r) of the
+// recomputed vectors, from the partials of the fused dual SpMV.  Writes ONLY
+// S_GAMMA and S_DELTA: k_pipelined_finalize of the iteration just finished
+// has already rotated S_GAMMA_PREV / S_ALPHA_PREV.
+__global__ void __launch_bounds__(BLOCK)
+k_pipelined_replace_finalize(const double* __restrict__ partials, int nblocks,
+                             double* scal) {
+    double g = 0.0, d = 0.0;
+    for (int i = threadIdx.x; i < nblocks; i += BLOCK) {
+        g += partials[i];
+        d += partials[MAXG + i];
+    }
+    g = block_reduce(g);
+    __syncthreads();
+    d = block_reduce(d);
+    if (threadIdx.x == 0) {
         scal[S_GAMMA] = g;
         scal[S_DELTA] = d;
     }
@@ -2976,6 +3170,97 @@ void spmv_sell(long nslices, long nrows, long rowbase, uintptr_t sellptr,
         reduce_partials(partials, (int)blocks, scal, dotslot, dot_accum, stream);
 }
 
+// Dual SpMV launchers (residual replacement).  ``b`` != 0 selects RESID,
+// ``partials`` != 0 the fused (x1,x1) / (y1,x1) partials; both return the
+// number of blocks launched (= partials written per half when fused).
+long spmv2_sell(long nslices, long nrows, uintptr_t sellptr, uintptr_t cols,
+                int col64, uintptr_t vals, uintptr_t x1, uintptr_t x2,
+                uintptr_t b, uintptr_t y1, uintptr_t y2, uintptr_t partials,
+                uintptr_t perm, uintptr_t stream) {
+    if (nrows == 0 || nslices == 0) return 0;
+    long blocks = (nslices * WAVE + BLOCK - 1) / BLOCK;
+    if (blocks > MAXG) blocks = MAXG;
+    dim3 g((unsigned)blocks), bl(BLOCK);
+    #define LAUNCH_SELL2(CT, RS, FD, PM) \
+        hipLaunchKernelGGL((k_spmv2_sell<CT, RS, FD, PM>), g, bl, 0, S(stream), \
+            nslices, nrows, (const long*)sellptr, (const CT*)cols, \
+            (const double*)vals, (const double*)x1, (const double*)x2, \
+            (const double*)b, (double*)y1, (double*)y2, (double*)partials, \
+            (const int*)perm)
+    #define DISP2_PM(CT, RS, FD) \
+        if (perm != 0) { LAUNCH_SELL2(CT, RS, FD, true); } \
+        else { LAUNCH_SELL2(CT, RS, FD, false); }
+    #define DISP2_RF(CT) \
+        if (b != 0) { if (partials != 0) { DISP2_PM(CT, true, true) } else { DISP2_PM(CT, true, false) } } \
+        else        { if (partials != 0) { DISP2_PM(CT, false, true) } else { DISP2_PM(CT, false, false) } }
+    if (col64) { DISP2_RF(long) } else { DISP2_RF(int) }
+    #undef DISP2_RF
+    #undef DISP2_PM
+    #undef LAUNCH_SELL2
+    check_hip("spmv2_sell");
+    return blocks;
+}
+
+long spmv2_bsell(long nslices, long nnodes, int dof, uintptr_t bptr,
+                 uintptr_t bcol, uintptr_t bvals, uintptr_t x1, uintptr_t x2,
+                 uintptr_t b, uintptr_t y1, uintptr_t y2, uintptr_t partials,
+                 uintptr_t stream) {
+    if (dof < 2 || dof > 4)
+        throw std::runtime_error("spmv2_bsell: dof must be 2/3/4");
+    if (nnodes == 0 || nslices == 0) return 0;
+    long blocks = (nslices * WAVE + BLOCK - 1) / BLOCK;
+    if (blocks > MAXG) blocks = MAXG;
+    dim3 g((unsigned)blocks), bl(BLOCK);
+    #define LBS2(D, RS, FD) \
+        hipLaunchKernelGGL((k_spmv2_bsell<D, RS, FD>), g, bl, 0, S(stream), \
+            nslices, nnodes, (const long*)bptr, (const int*)bcol, \
+            (const double*)bvals, (const double*)x1, (const double*)x2, \
+            (const double*)b, (double*)y1, (double*)y2, (double*)partials)
+    #define DISP_BS2(D) \
+        if (b != 0) { if (partials != 0) { LBS2(D, true, true); } else { LBS2(D, true, false); } } \
+        else        { if (partials != 0) { LBS2(D, false, true); } else { LBS2(D, false, false); } }
+    switch (dof) {
+        case 2: DISP_BS2(2) break;
+        case 3: DISP_BS2(3) break;
+        default: DISP_BS2(4) break;
+    }
+    #undef DISP_BS2
+    #undef LBS2
+    check_hip("spmv2_bsell");
+    return blocks;
+}
+
+// dof 1 = SELL rows (optional sigma perm), dof 2/3/4 = BSELL nodes
+long dot2_slices(long nslices, long nunits, int dof, uintptr_t r, uintptr_t w,
+                 uintptr_t perm, uintptr_t partials, uintptr_t stream) {
+    if (dof < 1 || dof > 4 || (dof > 1 && perm != 0))
+        throw std::runtime_error("dot2_slices: dof must be 1..4, perm only with dof 1");
+    if (nunits == 0 || nslices == 0) return 0;
+    long blocks = (nslices * WAVE + BLOCK - 1) / BLOCK;
+    if (blocks > MAXG) blocks = MAXG;
+    dim3 g((unsigned)blocks), bl(BLOCK);
+    #define LD2S(D, PM) \
+        hipLaunchKernelGGL((k_dot2_slices<D, PM>), g, bl, 0, S(stream), nslices, \
+            nunits, (const double*)r, (const double*)w, (const int*)perm, \
+            (double*)partials)
+    switch (dof) {
+        case 1: if (perm != 0) { LD2S(1, true); } else { LD2S(1, false); } break;
+        case 2: LD2S(2, false); break;
+        case 3: LD2S(3, false); break;
+        default: LD2S(4, false); break;
+    }
+    #undef LD2S
+    check_hip("dot2_slices");
+    return blocks;
+}
+
+void pipelined_replace_finalize(uintptr_t partials, int nblocks, uintptr_t scal,
+                                uintptr_t stream) {
+    hipLaunchKernelGGL(k_pipelined_replace_finalize, dim3(1), dim3(BLOCK), 0,
+                       S(stream), (const double*)partials, nblocks, (double*)scal);
+    check_hip("pipelined_replace_finalize");
+}
+
 void zero_scalars(uintptr_t scal, int i0, int count, uintptr_t stream) {
     hipLaunchKernelGGL(k_zero_scalars, dim3(1), dim3(BLOCK), 0, S(stream),
                        (double*)scal, i0, count);
@@ -3483,6 +3768,7 @@ PYBIND11_MODULE(_acg_kernels, m) {
     m.def("spmv", &spmv);
     m.def("spmv_binned", &spmv_binned);
     m.def("spmv_sell", &spmv_sell);
+    m.def("spmv2_sell", &spmv2_sell);
     m.def("zero_scalars", &zero_scalars);
     m.def("cg_prep_pt", &cg_prep_pt);
     m.def("cg_prep_rr", &cg_prep_rr);
@@ -3498,12 +3784,15 @@ PYBIND11_MODULE(_acg_kernels, m) {
     m.def("pipelined_fused", &pipelined_fused);
     m.def("sell_pipe", &sell_pipe);
     m.def("pipelined_finalize", &pipelined_finalize);
+    m.def("pipelined_replace_finalize", &pipelined_replace_finalize);
+    m.def("dot2_slices", &dot2_slices);
     m.def("pack_gather", &pack_gather);
     m.def("atomic_probe", &atomic_probe);
     m.def("cg_device", &cg_device);
     m.def("stencil_rowlen", &stencil_rowlen);
     m.def("stencil_fill", &stencil_fill);
     m.def("spmv_bsell", &spmv_bsell);
+    m.def("spmv2_bsell", &spmv2_bsell);
     m.def("spmv_bsell_daypx", &spmv_bsell_daypx);
     m.def("spmv_bsell_st", &spmv_bsell_st);
     m.attr("ST_NOSEND") = ST_NOSEND;

@@ -382,6 +382,101 @@ def spmv_bsell(bptr, bcol, bvals, nnodes: int, dof: int, x, y, *,
         scal[dotslot] = scal[dotslot] + d if dot_accum else d
 
 
+def _spmv2_finish(c1, c2, owner_block, nblocks: int, n: int, x1, y1, y2, b,
+                  partials) -> int:
+    """Outputs and block partials of a dual SpMV from the two products;
+    ``owner_block[row]`` is the 256-thread block (4 slices) that owns the
+    row in the kernel, which fixes where its dot terms land."""
+    o1 = b[:n] - c1 if b is not None else c1
+    y1[:n] = o1
+    y2[:n] = c2
+    if partials is not None:
+        xr = x1[:n]
+        g = torch.zeros(nblocks, dtype=torch.float64, device=x1.device)
+        d = torch.zeros(nblocks, dtype=torch.float64, device=x1.device)
+        g.index_add_(0, owner_block, xr * xr)
+        d.index_add_(0, owner_block, o1 * xr)
+        partials[:nblocks] = g
+        partials[MAXG:MAXG + nblocks] = d
+    return nblocks
+
+
+def spmv2_sell(sellptr, cols, vals, nrows, x1, x2, y1, y2, *, ncols: int,
+               b=None, partials=None, perm=None, C: int = 64) -> int:
+    """Dual SpMV (matches k_spmv2_sell): y1 = A x1 (b - A x1 with ``b``),
+    y2 = A x2; with ``partials`` the per-block sums of (x1,x1) and (y1,x1)
+    in partials[:nb] / partials[MAXG:MAXG + nb].  Returns nb."""
+    if vals.dtype != torch.float64:
+        raise TypeError(f"spmv2_sell: operator values must be float64, got {vals.dtype}")
+    nslices = sellptr.numel() - 1
+    if nslices <= 0 or nrows <= 0:
+        return 0
+    c1 = torch.zeros(nrows, dtype=torch.float64, device=x1.device)
+    c2 = torch.zeros(nrows, dtype=torch.float64, device=x1.device)
+    spmv_sell(sellptr, cols, vals, nrows, x1, c1, C=C, perm=perm)
+    spmv_sell(sellptr, cols, vals, nrows, x2, c2, C=C, perm=perm)
+    sellrow = torch.arange(nslices * C, device=x1.device)
+    owner = torch.zeros(nrows, dtype=torch.int64, device=x1.device)
+    if perm is not None:
+        rowof = perm[:nslices * C].long()
+        ok = rowof < nrows
+        owner[rowof[ok]] = sellrow[ok] // (4 * C)
+    else:
+        owner[:] = sellrow[:nrows] // (4 * C)
+    return _spmv2_finish(c1, c2, owner, (nslices + 3) // 4, nrows, x1, y1, y2,
+                         b, partials)
+
+
+def spmv2_bsell(bptr, bcol, bvals, nnodes: int, dof: int, x1, x2, y1, y2, *,
+                ncols: int, b=None, partials=None, C: int = 64) -> int:
+    """Dual Block-SELL SpMV (matches k_spmv2_bsell); see :func:`spmv2_sell`."""
+    if bvals.dtype != torch.float64:
+        raise TypeError(f"spmv2_bsell: operator values must be float64, got {bvals.dtype}")
+    nslices = bptr.numel() - 1
+    if nslices <= 0 or nnodes <= 0:
+        return 0
+    n = nnodes * dof
+    c1 = _bsell_contrib(bptr, bcol, bvals, nnodes, dof, x1, C=C)
+    c2 = _bsell_contrib(bptr, bcol, bvals, nnodes, dof, x2, C=C)
+    owner = torch.arange(n, device=x1.device) // (dof * 4 * C)
+    return _spmv2_finish(c1, c2, owner, (nslices + 3) // 4, n, x1, y1, y2, b,
+                         partials)
+
+
+def dot2_slices(r, w, nunits: int, dof: int, partials, *, perm=None,
+                C: int = 64) -> int:
+    """Block partials of (r,r) and (w,r) in the dual SpMV's block partition
+    (matches k_dot2_slices).  Returns the number of blocks."""
+    if nunits <= 0:
+        return 0
+    nslices = (nunits + C - 1) // C
+    nblocks = (nslices + 3) // 4
+    n = nunits * dof
+    unit = torch.arange(nslices * C, device=r.device)
+    owner = torch.zeros(nunits, dtype=torch.int64, device=r.device)
+    if perm is not None:
+        rowof = perm[:nslices * C].long()
+        ok = rowof < nunits
+        owner[rowof[ok]] = unit[ok] // (4 * C)
+    else:
+        owner[:] = unit[:nunits] // (4 * C)
+    owner = owner.repeat_interleave(dof)
+    g = torch.zeros(nblocks, dtype=torch.float64, device=r.device)
+    d = torch.zeros(nblocks, dtype=torch.float64, device=r.device)
+    g.index_add_(0, owner, r[:n] * r[:n])
+    d.index_add_(0, owner, w[:n] * r[:n])
+    partials[:nblocks] = g
+    partials[MAXG:MAXG + nblocks] = d
+    return nblocks
+
+
+def pipelined_replace_finalize(partials, nblocks: int, scal) -> None:
+    """scal[GAMMA] / scal[DELTA] from the two partial halves; nothing else
+    (matches k_pipelined_replace_finalize)."""
+    scal[S_GAMMA] = partials[:nblocks].sum()
+    scal[S_DELTA] = partials[MAXG:MAXG + nblocks].sum()
+
+
 def spmv_bsell_daypx(bptr, bcol, bvals, nnodes: int, dof: int, pold, rvec,
                      pnew, y, scal, partials, dotslot: int) -> None:
     """p_new = beta*p_old + r with beta = rr/rr_prev, y = A p_new, and

@@ -49,6 +49,8 @@ class SolveResult:
     # solve_block: block iteration at which the block broke down and the
     # columns were handed to solve_multi (0 = at initialisation, -1 = never)
     block_breakdown: int = -1
+    # pipelined CG: residual replacements performed (rr_period > 0)
+    nreplacements: int = 0
 
     @property
     def iters_per_s(self) -> float:
@@ -73,6 +75,8 @@ class SolveResult:
         if self.nouter:
             lines.insert(3, f"outer refinement sweeps: {self.nouter} "
                             f"({self.niterations} inner iterations)")
+        if self.nreplacements:
+            lines.insert(3, f"residual replacements: {self.nreplacements}")
         if self.halo_bytes_sent:
             per_it = self.halo_bytes_sent / max(self.niterations, 1)
             lines.append(
@@ -228,6 +232,12 @@ def block_results(solver: str, ncols: int, active: list,
 def cg_flops_per_iter(nnz_full: int, n: int) -> float:
     """Flops per classic-CG iteration: SpMV 2*nnz + 2 dots + 3 axpy-likes."""
     return 2.0 * nnz_full + 10.0 * n
+
+
+def replacement_flops(nnz_full: int, n: int) -> float:
+    """Flops of one residual replacement of the pipelined CG: four SpMVs,
+    the subtraction from b and the two dots."""
+    return 8.0 * nnz_full + 5.0 * n
 
 
 def cg_bytes_per_iter(nnz_full: int, n: int, colbytes: int = 4) -> float:

@@ -25,7 +25,7 @@ from ..ops import torch_ref as ops
 from ..part.subdomain import LocalSystem
 from .base import (ColumnTolerances, SolveResult, block_results,
                    cg_flops_per_iter, check_multi_shapes, next_multi_k,
-                   refine, solve_multi_by_column)
+                   refine, replacement_flops, solve_multi_by_column)
 
 
 class CGSolverCPU:
@@ -451,7 +451,16 @@ class CGSolverCPU:
     # -- pipelined CG (reference acgsolverhip_solve_pipelined, §3.3) ------
 
     def solve_pipelined(self, b: torch.Tensor, x: torch.Tensor, maxits: int = 100,
-                        res_atol: float = 0.0, res_rtol: float = 1e-9) -> SolveResult:
+                        res_atol: float = 0.0, res_rtol: float = 1e-9,
+                        rr_period: int = 0) -> SolveResult:
+        """``rr_period`` > 0: residual replacement.  After the update of
+        every iteration k with (k + 1) % rr_period == 0 the four recurrence
+        vectors are recomputed from x and p: r = b - A x, t = A p, w = A r,
+        z = A t.  gamma_prev / alpha_prev stay; the next iteration's
+        gamma = (r,r) and delta = (w,r) come from the replaced vectors.
+        0 (the default) is the plain Ghysels-Vanroose recurrence."""
+        if rr_period < 0:
+            raise ValueError(f"rr_period must not be negative, got {rr_period}")
         res = SolveResult(solver="cg-pipelined-cpu", maxits=maxits,
                           res_atol=res_atol, res_rtol=res_rtol,
                           nranks=self.comm.size if self.comm else 1)
@@ -466,6 +475,11 @@ class CGSolverCPU:
         z = self._vec()
         t = self._vec()
         p = self._vec()
+        if rr_period:
+            # t and p become SpMV inputs: they need ghost tails
+            tfull = self._vec(nghost=True)
+            pfull = self._vec(nghost=True)
+            t, p = tfull[:n], pfull[:n]
         self._spmv(x, tmp)
         r[:n] = b[:n] - tmp
         self._spmv(r, w)  # w = A r  (writes w[:n])
@@ -498,9 +512,17 @@ class CGSolverCPU:
             w[:n] -= alpha * z
             gamma_prev, alpha_prev = gamma, alpha
             res.niterations = k + 1
+            if rr_period and (k + 1) % rr_period == 0:
+                self._spmv(x, tmp)
+                r[:n] = b[:n] - tmp
+                self._spmv(pfull, t)
+                self._spmv(r, w)
+                self._spmv(tfull, z)
+                res.nreplacements += 1
         res.tsolve = time.perf_counter() - t0
         nnz_full = self.local.nnzA + self.local.nnzO
-        res.nflops = res.niterations * (cg_flops_per_iter(nnz_full, n) + 8.0 * n)
+        res.nflops = (res.niterations * (cg_flops_per_iter(nnz_full, n) + 8.0 * n)
+                      + res.nreplacements * replacement_flops(nnz_full, n))
         res.halo_bytes_sent = self.halo.bytes_sent
         res.halo_msgs_sent = self.halo.nmsgs_sent
         return res

@@ -36,7 +36,7 @@ from ..ops import gpu_ops as ops
 from ..part.subdomain import LocalSystem
 from .base import (ColumnTolerances, SolveResult, block_results,
                    cg_flops_per_iter, check_multi_shapes, next_multi_k,
-                   refine, solve_multi_by_column)
+                   refine, replacement_flops, solve_multi_by_column)
 
 
 # Whether a solver builds BSELL-ST without being asked (force_format or
@@ -197,6 +197,9 @@ class CGSolverHIP:
         # system two groups of 4 were nevertheless measured faster than
         # one of 8 (profiles/multi_rhs.md, NOTES.md).
         self.multi_group = 8
+        # solve_pipelined(rr_period > 0): False forces the four-SpMV
+        # replacement where the dual-SpMV fast path would apply (A/B, tests)
+        self._rr_fast = True
 
     def _pick_format(self, L, up, use_sell: bool, force: str | None) -> None:
         """Choose the matA operator format (reference analog: the choice
@@ -414,10 +417,11 @@ class CGSolverHIP:
                       file=sys.stderr)
             return None
 
-    def _count_work(self, res: SolveResult, flops_per_it: float) -> None:
+    def _count_work(self, res: SolveResult, flops_per_it: float,
+                    extra_flops: float = 0.0) -> None:
         """Always-on counters of a finished solve (reference
         cghip.h:109-118)."""
-        res.nflops = res.niterations * flops_per_it
+        res.nflops = res.niterations * flops_per_it + extra_flops
         res.halo_bytes_sent = self.halo.bytes_sent
         res.halo_msgs_sent = self.halo.nmsgs_sent
         self.niterations_total += res.niterations
@@ -1505,7 +1509,8 @@ class CGSolverHIP:
     def solve_pipelined(self, b: torch.Tensor, x: torch.Tensor, maxits: int = 100,
                         res_atol: float = 0.0, res_rtol: float = 1e-9,
                         use_graph: bool | None = None,
-                        megafuse: bool | None = None) -> SolveResult:
+                        megafuse: bool | None = None,
+                        rr_period: int = 0) -> SolveResult:
         """Pipelined (Ghysels-Vanroose) CG: ONE 2-double allreduce per
         iteration, overlapped with the halo + SpMV of q = A w
         (reference acgsolverhip_solve_pipelined, cghip.c:1187-1933).
@@ -1523,7 +1528,27 @@ class CGSolverHIP:
         previous gamma, so on the converging iteration 1-2 extra (valid)
         updates have already been applied to x; reported
         niterations/rnrm2 match the eager path.
+
+        ``rr_period`` > 0: residual replacement (beyond reference; PETSc's
+        KSPPIPECGRR idea with a fixed period).  After the update of every
+        iteration k with (k + 1) % rr_period == 0 the recurrence vectors
+        are recomputed from xi and p, eagerly on the solve's stream and
+        outside any graph: (r, t) = (b - A xi, A p), then (w, z) =
+        (A r, A t) with gamma = (r,r), delta = (w,r); gamma_prev and
+        alpha_prev keep the rotation of the iteration just finished.  One
+        rank without matO on SELL, sigma-SELL or BSELL takes two dual-SpMV
+        launches plus a finalize; every other configuration runs the same
+        algebra as four ``_spmv_overlapped`` calls and ``dot2`` (or, with
+        the fast path only switched off by ``_rr_fast``, ``dot2_slices``:
+        the dual kernels' summation order, same bits).  The next
+        iteration's allreduce picks up the replaced local gamma/delta.
+        ``nreplacements`` counts the replacements inside the reported
+        iterations.  0 (default) issues exactly the launches of the plain
+        solve on the plain workspaces.
         """
+        if rr_period < 0:
+            raise ValueError(f"rr_period must not be negative, got {rr_period}")
+        rr_period = int(rr_period)
         res = SolveResult(solver="cg-hip-pipelined", maxits=maxits,
                           res_atol=res_atol, res_rtol=res_rtol,
                           nranks=self.comm.size if self.comm else 1)
@@ -1533,8 +1558,13 @@ class CGSolverHIP:
         scal = self.scal
         mega = self.megafuse_auto if megafuse is None else (megafuse and self.can_megafuse)
         wskey = f"pipelined{'_mega' if mega else ''}"
-        names = [("r", True), ("w", True), ("z", False), ("t", False),
-                 ("p", False), ("tmp", False), ("xi", True)]
+        if rr_period:
+            # a workspace (and graphs) of its own: t and p are SpMV inputs
+            # of the replacement and carry ghost tails here
+            wskey += "_rr"
+        names = [("r", True), ("w", True), ("z", False),
+                 ("t", bool(rr_period)), ("p", bool(rr_period)),
+                 ("tmp", False), ("xi", True)]
         names += [("w2", True)] if mega else [("q", False)]
         ws = self._workspace(wskey, names)
         r, w, z, t, p, tmp, xi = (ws["r"], ws["w"], ws["z"], ws["t"],
@@ -1612,6 +1642,52 @@ class CGSolverHIP:
                                       mato=True)
                 nb += nbO
             S.pipelined_finalize(self.partials, nb, scal, first)
+
+        rr_dual_ok = (rr_period > 0 and serial
+                      and L.nnzO == 0 and self.matfree is None
+                      and (self.bsell is not None or self.sell is not None))
+        rr_fast = rr_dual_ok and self._rr_fast
+
+        def replace(wdst):
+            """Residual replacement; ``wdst`` is the w buffer the next
+            iteration gathers from."""
+            with self.prof.span("replace"):
+                if rr_fast:
+                    kw = dict(ncols=self.nlocal)
+                    if self.bsell is not None:
+                        bptr, bcol, bvals, dof = self.bsell
+                        S.spmv2_bsell(bptr, bcol, bvals, n // dof, dof, xi, p,
+                                      r, t, b=b, **kw)
+                        nb = S.spmv2_bsell(bptr, bcol, bvals, n // dof, dof,
+                                           r, t, wdst, z,
+                                           partials=self.partials, **kw)
+                    else:
+                        sp, sc, sv = self.sell
+                        kw["perm"] = self.sell_perm
+                        S.spmv2_sell(sp, sc, sv, n, xi, p, r, t, b=b, **kw)
+                        nb = S.spmv2_sell(sp, sc, sv, n, r, t, wdst, z,
+                                          partials=self.partials, **kw)
+                    S.pipelined_replace_finalize(self.partials, nb, scal)
+                else:
+                    self._spmv_overlapped(xi, tmp)
+                    torch.sub(b[:n], tmp, out=r[:n])
+                    self._spmv_overlapped(p, t)
+                    self._spmv_overlapped(r, wdst)
+                    self._spmv_overlapped(t, z)
+                    if not rr_dual_ok:
+                        S.dot2(r, wdst, self.partials, scal, n)
+                    else:
+                        # fast path switched off (_rr_fast): the dots in
+                        # the dual kernels' summation order, so the two
+                        # paths give the same gamma / delta bit for bit
+                        if self.bsell is not None:
+                            dof = self.bsell[3]
+                            nb = S.dot2_slices(r, wdst, n // dof, dof,
+                                               self.partials)
+                        else:
+                            nb = S.dot2_slices(r, wdst, n, 1, self.partials,
+                                               perm=self.sell_perm)
+                        S.pipelined_replace_finalize(self.partials, nb, scal)
         # lag-1 convergence pipeline: gamma_k is copied to the host as soon
         # as its allreduce lands, but the host *reads* it one iteration
         # later -- the test still runs for every iteration, the host just
@@ -1705,6 +1781,8 @@ class CGSolverHIP:
                 # same slot/value as the eager path: the ALLREDUCED
                 # previous gamma, snapshotted inside the replay
                 ring.push(k, gsnap, cur)
+                if rr_period and (k + 1) % rr_period == 0:
+                    replace((w2 if k % 2 == 0 else w) if mega else w)
                 k += 1
                 res.niterations = k
                 continue
@@ -1779,6 +1857,8 @@ class CGSolverHIP:
                     dgraph = self._capture_dist(body_dist, dist_failed_key)
                     if dgraph is not None:
                         self._graphs[dist_key] = dgraph
+            if rr_period and (k + 1) % rr_period == 0:
+                replace((w2 if k % 2 == 0 else w) if mega else w)
             k += 1
             res.niterations = k
         if not converged:
@@ -1793,6 +1873,9 @@ class CGSolverHIP:
             res.rnrm2 = math.sqrt(max(gamma_host, 0.0))
         res.converged = converged
         nnz_full = self.local.nnzA + self.local.nnzO
-        self._count_work(res, cg_flops_per_iter(nnz_full, n) + 8.0 * n)
+        if rr_period:
+            res.nreplacements = res.niterations // rr_period
+        self._count_work(res, cg_flops_per_iter(nnz_full, n) + 8.0 * n,
+                         res.nreplacements * replacement_flops(nnz_full, n))
         self._annotate_profile(res)
         return res

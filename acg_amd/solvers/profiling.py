@@ -102,6 +102,14 @@ def annotate_op_stats(res: SolveResult, local, ops_times: dict,
         fl, by = model.get(name, (0.0, 0.0))
         st.flops = fl * it
         st.bytes = by * it
+    if "replace" in ops_times:
+        # residual replacement of the pipelined CG: counted per call, not per
+        # iteration; two matrix reads on the dual-SpMV path (modelled here),
+        # four on the fallback path, whose SpMVs also appear under spmvA/O
+        st = ops_times["replace"]
+        nnz = nnzA + nnzO
+        st.flops = (8.0 * nnz + 5.0 * n) * st.count
+        st.bytes = (2.0 * nnz * (8 + colb) + 9.0 * 8 * n) * st.count
     res.ops = ops_times
 
 

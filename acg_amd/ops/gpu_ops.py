@@ -37,7 +37,7 @@ S_GAMMA_PREV = K.S_GAMMA_PREV
 S_ALPHA_PREV = K.S_ALPHA_PREV
 S_NSLOTS = K.S_NSLOTS
 MAXG = K.MAXG
-K_ST_TILE = 256  # nodes per BSELL-ST tile = one workgroup of k_spmv_bsell_st
+K_ST_TILE = K.ST_TILE  # nodes per BSELL-ST tile = one workgroup of k_spmv_bsell_st
 
 
 def _stream() -> int:
@@ -175,7 +175,7 @@ def spmv_binned(rowptr: torch.Tensor, colidx: torch.Tensor, vals: torch.Tensor,
 
 # SELL kernel variant bits (see kernels.hip): +1 non-temporal vals/cols,
 # +2 XCD-aware block swizzle, +4 unroll-8.
-SELL_NT, SELL_SWZ, SELL_U8 = 1, 2, 4
+SELL_NT, SELL_SWZ, SELL_U8 = K.SELL_NT, K.SELL_SWZ, K.SELL_U8
 # A/B on MI355X (tools/spmv_bench.py, Queen-shaped 326M nnz): base 5.53,
 # NT 5.66, NT+U8 5.78 TB/s (92% of the ~6.3 TB/s achievable); SWZ slightly
 # negative (x is L3-resident, natural slice order already L2-local).
@@ -692,7 +692,7 @@ def pipelined_fused(z, t, p, x, r, w, q, scal: torch.Tensor,
                       nt_update, _stream())
 
 
-BAR_STATE_WORDS = 400  # shared with kernels.hip (flat + hierarchical v3)
+BAR_STATE_WORDS = K.BAR_STATE_WORDS  # flat + hierarchical v3 barrier state
 
 
 def cg_device(sellptr: torch.Tensor, cols: torch.Tensor, vals: torch.Tensor,

@@ -34,7 +34,8 @@
 //      kernels of the batched classic CG,
 //   8. block CG over the same multivectors: K x K Gram reductions, the
 //      fused block update, the Cholesky-QR re-orthonormalisation and the
-//      two one-workgroup dense coefficient kernels.
+//      two one-workgroup dense coefficient kernels,
+//   9. the host side: dispatch helpers, one launcher per operation, pybind.
 //
 // The scalar slab layout (fp64 slots) is shared with solvers/hip.py:
 #define S_RR 0         // (r,r) current
@@ -79,6 +80,7 @@
 #include <vector>
 #include <stdexcept>
 #include <string>
+#include <type_traits>
 
 namespace py = pybind11;
 
@@ -1446,194 +1448,6 @@ k_stencil_fill(long nrows_nodes, long row0_node, int gx, int gy, int gz,
     }
 }
 
-void spmv_bsell(long nslices, long nnodes, int dof, uintptr_t bptr,
-                uintptr_t bcol, uintptr_t bvals, uintptr_t x, uintptr_t y,
-                uintptr_t partials, uintptr_t scal, int dotslot,
-                bool dot_accum, bool val32, uintptr_t stream) {
-    if (nnodes == 0) return;
-    long blocks = (nslices * WAVE + BLOCK - 1) / BLOCK;
-    if (blocks > MAXG) blocks = MAXG;
-    const bool fuse = partials != 0 && dotslot >= 0;
-    dim3 g((unsigned)blocks), b(BLOCK);
-    if (val32) {
-        // fp32-stored values, same pair-major element order
-        #define LBS32(D, FD) \
-            hipLaunchKernelGGL((k_spmv_bsell<D, FD, float>), g, b, 0, (hipStream_t)stream, \
-                nslices, nnodes, (const long*)bptr, (const int*)bcol, \
-                (const float*)bvals, (const double*)x, (double*)y, (double*)partials)
-        switch (dof) {
-            case 2: if (fuse) { LBS32(2, true); } else { LBS32(2, false); } break;
-            case 3: if (fuse) { LBS32(3, true); } else { LBS32(3, false); } break;
-            case 4: if (fuse) { LBS32(4, true); } else { LBS32(4, false); } break;
-            default: throw std::runtime_error("spmv_bsell: dof must be 2/3/4");
-        }
-        #undef LBS32
-        check_hip("spmv_bsell_f32");
-        if (fuse) {
-            hipLaunchKernelGGL(k_reduce_partials, dim3(1), dim3(BLOCK), 0,
-                               (hipStream_t)stream, (const double*)partials,
-                               (int)blocks, (double*)scal, dotslot, dot_accum ? 1 : 0);
-            check_hip("spmv_bsell_reduce");
-        }
-        return;
-    }
-    #define LBS(D, FD) \
-        hipLaunchKernelGGL((k_spmv_bsell<D, FD>), g, b, 0, (hipStream_t)stream, \
-            nslices, nnodes, (const long*)bptr, (const int*)bcol, \
-            (const double*)bvals, (const double*)x, (double*)y, (double*)partials)
-    switch (dof) {
-        case 2: if (fuse) { LBS(2, true); } else { LBS(2, false); } break;
-        case 3: if (fuse) { LBS(3, true); } else { LBS(3, false); } break;
-        case 4: if (fuse) { LBS(4, true); } else { LBS(4, false); } break;
-        default: throw std::runtime_error("spmv_bsell: dof must be 2/3/4");
-    }
-    #undef LBS
-    check_hip("spmv_bsell");
-    if (fuse) {
-        hipLaunchKernelGGL(k_reduce_partials, dim3(1), dim3(BLOCK), 0,
-                           (hipStream_t)stream, (const double*)partials,
-                           (int)blocks, (double*)scal, dotslot, dot_accum ? 1 : 0);
-        check_hip("spmv_bsell_reduce");
-    }
-}
-
-// Returns the number of blocks launched (= partials written when fused).
-// ``max_blocks`` > 0 caps the grid (grid-stride over tiles takes the rest).
-long spmv_bsell_st(long ntiles, long nslices, long nnodes, int dof, int qmax,
-                   uintptr_t sptr, uintptr_t spl, uintptr_t scol, uintptr_t sq,
-                   uintptr_t svals, uintptr_t nrecv, uintptr_t x, uintptr_t y,
-                   uintptr_t partials, uintptr_t scal, int dotslot,
-                   bool dot_accum, long max_blocks, uintptr_t stream) {
-    if (nnodes == 0 || ntiles == 0) return 0;
-    if (ntiles != (nslices + BLOCK / WAVE - 1) / (BLOCK / WAVE)
-        || nslices != (nnodes + WAVE - 1) / WAVE)
-        throw std::invalid_argument("spmv_bsell_st: tile/slice/node counts disagree");
-    if (qmax < 0 || qmax >= ST_NOSEND)
-        throw std::invalid_argument("spmv_bsell_st: qmax must be in [0, 255)");
-    const size_t lds = (size_t)qmax * dof * BLOCK * sizeof(double);
-    if (lds > 96 * 1024)
-        throw std::invalid_argument("spmv_bsell_st: qmax * dof needs more than 96 KiB of LDS");
-    long blocks = ntiles;
-    if (blocks > MAXG) blocks = MAXG;
-    if (max_blocks > 0 && blocks > max_blocks) blocks = max_blocks;
-    const bool fuse = partials != 0 && dotslot >= 0;
-    dim3 g((unsigned)blocks), b(BLOCK);
-    #define LST(D, FD) do { \
-        if (lds > 48 * 1024 && hipFuncSetAttribute( \
-                (const void*)k_spmv_bsell_st<D, FD>, \
-                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) \
-            throw std::runtime_error("spmv_bsell_st: cannot raise the LDS limit"); \
-        hipLaunchKernelGGL((k_spmv_bsell_st<D, FD>), g, b, lds, (hipStream_t)stream, \
-            ntiles, nslices, nnodes, (const long*)sptr, (const int*)spl, \
-            (const int*)scol, (const unsigned char*)sq, (const double*)svals, \
-            (const unsigned char*)nrecv, (const double*)x, (double*)y, \
-            (double*)partials); } while (0)
-    switch (dof) {
-        case 2: if (fuse) { LST(2, true); } else { LST(2, false); } break;
-        case 3: if (fuse) { LST(3, true); } else { LST(3, false); } break;
-        case 4: if (fuse) { LST(4, true); } else { LST(4, false); } break;
-        default: throw std::runtime_error("spmv_bsell_st: dof must be 2/3/4");
-    }
-    #undef LST
-    check_hip("spmv_bsell_st");
-    if (fuse) {
-        hipLaunchKernelGGL(k_reduce_partials, dim3(1), dim3(BLOCK), 0,
-                           (hipStream_t)stream, (const double*)partials,
-                           (int)blocks, (double*)scal, dotslot, dot_accum ? 1 : 0);
-        check_hip("spmv_bsell_st_reduce");
-    }
-    return blocks;
-}
-
-void spmv_bsell_daypx(long nslices, long nnodes, int dof, uintptr_t bptr,
-                      uintptr_t bcol, uintptr_t bvals, uintptr_t pold,
-                      uintptr_t rvec, uintptr_t pnew, uintptr_t y,
-                      uintptr_t scal, uintptr_t partials, int dotslot,
-                      uintptr_t stream) {
-    if (nnodes == 0) return;
-    long blocks = (nslices * WAVE + BLOCK - 1) / BLOCK;
-    if (blocks > MAXG) blocks = MAXG;
-    dim3 g((unsigned)blocks), b(BLOCK);
-    #define LBD(D) \
-        hipLaunchKernelGGL((k_spmv_bsell_daypx<D>), g, b, 0, (hipStream_t)stream, \
-            nslices, nnodes, (const long*)bptr, (const int*)bcol, \
-            (const double*)bvals, (const double*)pold, (const double*)rvec, \
-            (double*)pnew, (double*)y, (const double*)scal, (double*)partials)
-    switch (dof) {
-        case 2: LBD(2); break;
-        case 3: LBD(3); break;
-        case 4: LBD(4); break;
-        default: throw std::runtime_error("spmv_bsell_daypx: dof must be 2/3/4");
-    }
-    #undef LBD
-    check_hip("spmv_bsell_daypx");
-    hipLaunchKernelGGL(k_reduce_partials, dim3(1), dim3(BLOCK), 0,
-                       (hipStream_t)stream, (const double*)partials,
-                       (int)blocks, (double*)scal, dotslot, 0);
-    check_hip("spmv_bsell_daypx_reduce");
-}
-
-void stencil_blocklen(long nnodes, int gx, int gy, int gz, long nown_nodes,
-                      uintptr_t zs_of_plane, uintptr_t pb, uintptr_t offs,
-                      int ksten, uintptr_t blocklen, uintptr_t stream) {
-    hipLaunchKernelGGL(k_stencil_blocklen, dim3((unsigned)elem_grid(nnodes)),
-                       dim3(BLOCK), 0, (hipStream_t)stream,
-                       nnodes, gx, gy, gz, nown_nodes, (const int*)zs_of_plane,
-                       (const long*)pb, (const double*)offs, ksten,
-                       (long*)blocklen);
-    check_hip("stencil_blocklen");
-}
-
-void stencil_bfill(long nnodes, int gx, int gy, int gz, int dof,
-                   long nown_nodes, uintptr_t zs_of_plane, uintptr_t pb,
-                   uintptr_t offs, int ksten, uintptr_t blocks_md,
-                   uintptr_t bptr, uintptr_t bcol, uintptr_t bvals,
-                   uintptr_t stream) {
-    dim3 g((unsigned)elem_grid(nnodes)), b(BLOCK);
-    #define LBF(D) \
-        hipLaunchKernelGGL((k_stencil_bfill<D>), g, b, 0, (hipStream_t)stream, \
-            nnodes, gx, gy, gz, nown_nodes, (const int*)zs_of_plane, \
-            (const long*)pb, (const double*)offs, ksten, \
-            (const double*)blocks_md, (const long*)bptr, (int*)bcol, \
-            (double*)bvals)
-    switch (dof) {
-        case 2: LBF(2); break;
-        case 3: LBF(3); break;
-        case 4: LBF(4); break;
-        default: throw std::runtime_error("stencil_bfill: dof must be 2/3/4");
-    }
-    #undef LBF
-    check_hip("stencil_bfill");
-}
-
-void stencil_rowlen(long nrows_nodes, long row0_node, int gx, int gy, int gz,
-                    int dof, long nown_nodes, uintptr_t zs_of_plane,
-                    uintptr_t pb, uintptr_t offs, int ksten, int filter_ghost,
-                    uintptr_t rowlen, uintptr_t stream) {
-    hipLaunchKernelGGL(k_stencil_rowlen, dim3((unsigned)elem_grid(nrows_nodes)),
-                       dim3(BLOCK), 0, (hipStream_t)stream,
-                       nrows_nodes, row0_node, gx, gy, gz, dof, nown_nodes,
-                       (const int*)zs_of_plane, (const long*)pb,
-                       (const double*)offs, ksten, filter_ghost, (long*)rowlen);
-    check_hip("stencil_rowlen");
-}
-
-void stencil_fill(long nrows_nodes, long row0_node, int gx, int gy, int gz,
-                  int dof, long nown_nodes, uintptr_t zs_of_plane,
-                  uintptr_t pb, uintptr_t offs, int ksten, uintptr_t blocks,
-                  int filter_ghost, uintptr_t sellptr, uintptr_t cols,
-                  uintptr_t vals, uintptr_t stream) {
-    const long nrows = nrows_nodes * dof;
-    hipLaunchKernelGGL(k_stencil_fill, dim3((unsigned)elem_grid(nrows)),
-                       dim3(BLOCK), 0, (hipStream_t)stream,
-                       nrows_nodes, row0_node, gx, gy, gz, dof, nown_nodes,
-                       (const int*)zs_of_plane, (const long*)pb,
-                       (const double*)offs, ksten, (const double*)blocks,
-                       filter_ghost, (const long*)sellptr, (int*)cols,
-                       (double*)vals);
-    check_hip("stencil_fill");
-}
-
 // ---------------------------------------------------------------------------
 // MATRIX-FREE stencil operator (dof=1, constant coefficients -- 5/7/27-pt
 // Poisson-type).  The assembled operator re-reads 12 B/nnz of vals+cols per
@@ -1873,110 +1687,6 @@ k_stencil_pipe7(long plane_nodes, int gx, int z0, int z1, int gz,
         partials[partials_off + blockIdx.x] = g;
         partials[MAXG + partials_off + blockIdx.x] = d;
     }
-}
-
-void stencil_spmv7(long plane_nodes, int gx, int z0, int z1, int gz,
-                   long nown_nodes, uintptr_t pb, double diag,
-                   double wxm, double wxp, double wym, double wyp,
-                   double wzm, double wzp, uintptr_t x, uintptr_t y,
-                   uintptr_t partials, uintptr_t scal, int dotslot,
-                   bool dot_accum, uintptr_t stream) {
-    if (plane_nodes == 0 || z1 <= z0) return;
-    long blocks = (plane_nodes + BLOCK - 1) / BLOCK;
-    if (blocks > MAXG) blocks = MAXG;
-    const bool fuse = partials != 0 && dotslot >= 0;
-    dim3 g((unsigned)blocks), b(BLOCK);
-    #define LS7(FD) \
-        hipLaunchKernelGGL((k_stencil_spmv7<FD>), g, b, 0, (hipStream_t)stream, \
-            plane_nodes, gx, z0, z1, gz, nown_nodes, (const long*)pb, diag, \
-            wxm, wxp, wym, wyp, wzm, wzp, (const double*)x, (double*)y, \
-            (double*)partials)
-    if (fuse) { LS7(true); } else { LS7(false); }
-    #undef LS7
-    check_hip("stencil_spmv7");
-    if (fuse) {
-        hipLaunchKernelGGL(k_reduce_partials, dim3(1), dim3(BLOCK), 0,
-                           (hipStream_t)stream, (const double*)partials,
-                           (int)blocks, (double*)scal, dotslot, dot_accum ? 1 : 0);
-        check_hip("stencil_spmv7_reduce");
-    }
-}
-
-long stencil_pipe7(long plane_nodes, int gx, int z0, int z1, int gz,
-                   long border_base, long nown_nodes, uintptr_t pb,
-                   double diag, double wxm, double wxp, double wym,
-                   double wyp, double wzm, double wzp, uintptr_t w_old,
-                   uintptr_t qpart, uintptr_t z, uintptr_t t, uintptr_t p,
-                   uintptr_t xv, uintptr_t r, uintptr_t w_new, uintptr_t scal,
-                   int first, uintptr_t partials, long partials_off,
-                   uintptr_t stream) {
-    if (plane_nodes == 0 || z1 <= z0) return 0;
-    long blocks = (plane_nodes + BLOCK - 1) / BLOCK;
-    const long cap = (partials_off == 0) ? (MAXG - 1024) : (MAXG - partials_off);
-    if (blocks > cap) blocks = cap;  // see sell_pipe
-    dim3 g((unsigned)blocks), b(BLOCK);
-    hipLaunchKernelGGL(k_stencil_pipe7, g, b, 0, (hipStream_t)stream,
-                       plane_nodes, gx, z0, z1, gz, border_base, nown_nodes,
-                       (const long*)pb, diag, wxm, wxp, wym, wyp, wzm, wzp,
-                       (const double*)w_old, (double*)qpart, (double*)z,
-                       (double*)t, (double*)p, (double*)xv, (double*)r,
-                       (double*)w_new, (const double*)scal, first,
-                       (double*)partials, partials_off);
-    check_hip("stencil_pipe7");
-    return blocks;
-}
-
-void stencil_spmv(long nrows_nodes, long row0_node, int gx, int gy, int gz,
-                  long nown_nodes, uintptr_t zs_of_plane, uintptr_t pb,
-                  uintptr_t offs, int ksten, double diag, uintptr_t x,
-                  uintptr_t y, bool mato, uintptr_t partials, uintptr_t scal,
-                  int dotslot, bool dot_accum, uintptr_t stream) {
-    if (nrows_nodes == 0) return;
-    const long blocks = elem_grid(nrows_nodes);
-    const bool fuse = partials != 0 && dotslot >= 0;
-    dim3 g((unsigned)blocks), b(BLOCK);
-    #define LMS(MATO, FD) \
-        hipLaunchKernelGGL((k_stencil_spmv<MATO, FD>), g, b, 0, \
-            (hipStream_t)stream, nrows_nodes, row0_node, gx, gy, gz, \
-            nown_nodes, (const int*)zs_of_plane, (const long*)pb, \
-            (const double*)offs, ksten, diag, (const double*)x, (double*)y, \
-            (double*)partials)
-    if (mato) { if (fuse) { LMS(true, true); } else { LMS(true, false); } }
-    else      { if (fuse) { LMS(false, true); } else { LMS(false, false); } }
-    #undef LMS
-    check_hip("stencil_spmv");
-    if (fuse) {
-        hipLaunchKernelGGL(k_reduce_partials, dim3(1), dim3(BLOCK), 0,
-                           (hipStream_t)stream, (const double*)partials,
-                           (int)blocks, (double*)scal, dotslot, dot_accum ? 1 : 0);
-        check_hip("stencil_spmv_reduce");
-    }
-}
-
-long stencil_pipe(long nrows_nodes, long row0_node, long border_base,
-                  int gx, int gy, int gz, long nown_nodes,
-                  uintptr_t zs_of_plane, uintptr_t pb, uintptr_t offs,
-                  int ksten, double diag, uintptr_t w_old, uintptr_t qpart,
-                  uintptr_t z, uintptr_t t, uintptr_t p, uintptr_t xv,
-                  uintptr_t r, uintptr_t w_new, uintptr_t scal, int first,
-                  uintptr_t partials, long partials_off, bool mato,
-                  uintptr_t stream) {
-    if (nrows_nodes == 0) return 0;
-    long blocks = elem_grid(nrows_nodes);
-    const long cap = (partials_off == 0) ? (MAXG - 1024) : (MAXG - partials_off);
-    if (blocks > cap) blocks = cap;  // see sell_pipe
-    dim3 g((unsigned)blocks), b(BLOCK);
-    #define LMP(MATO) \
-        hipLaunchKernelGGL((k_stencil_pipe<MATO>), g, b, 0, (hipStream_t)stream, \
-            nrows_nodes, row0_node, border_base, gx, gy, gz, nown_nodes, \
-            (const int*)zs_of_plane, (const long*)pb, (const double*)offs, \
-            ksten, diag, (const double*)w_old, (double*)qpart, (double*)z, \
-            (double*)t, (double*)p, (double*)xv, (double*)r, (double*)w_new, \
-            (const double*)scal, first, (double*)partials, partials_off)
-    if (mato) { LMP(true); } else { LMP(false); }
-    #undef LMP
-    check_hip("stencil_pipe");
-    return blocks;
 }
 
 // ---------------------------------------------------------------------------
@@ -2982,18 +2692,135 @@ k_block_coef_beta(const double* __restrict__ partials, int nblocks,
 // host-side launchers (pybind).  Tensors arrive as raw device pointers +
 // sizes + the caller's HIP stream handle (torch.cuda.current_stream().cuda_stream);
 // no torch C++ dependency, no hipify, plain HIP throughout.
+//
+// A launcher validates, sizes the grid, then turns its runtime selectors
+// into template arguments with the dispatch helpers below and launches
+// through launch().  Every instantiation that exists is spelled as a
+// kernel<...> expression inside a launcher; nothing else instantiates one.
 
 using std::uintptr_t;
 
 static inline hipStream_t S(uintptr_t s) { return (hipStream_t)s; }
 
+// -- dispatch helpers: runtime selector -> compile-time argument ------------
+// Each calls the generic lambda ``f`` with a tag object whose type carries
+// the value.  A tag parameter converts to its value in a constant
+// expression (``k<d, fd>``); a lambda nested inside needs it re-declared
+// as a constexpr local first (``constexpr int D = d;``), since a captured
+// parameter is no constant.
+
+template <typename T> struct type_tag { using type = T; };
+
+template <typename F>
+static inline void dispatch_bool(bool v, F&& f) {
+    if (v) f(std::true_type{}); else f(std::false_type{});
+}
+
+template <typename F>
+static inline void dispatch_bool(bool v0, bool v1, F&& f) {
+    dispatch_bool(v0, [&](auto b0) {
+        dispatch_bool(v1, [&](auto b1) { f(b0, b1); });
+    });
+}
+
+// ``v`` must be one of Vs..., else Err(who + rule) is thrown
+template <typename Err, int... Vs, typename F>
+static inline void dispatch_int(int v, const char* who, const char* rule, F&& f) {
+    const bool hit =
+        ((v == Vs ? (f(std::integral_constant<int, Vs>{}), true) : false) || ...);
+    if (!hit) throw Err(std::string(who) + rule);
+}
+
+template <typename F>
+static inline void dispatch_dof(int dof, const char* who, F&& f) {
+    dispatch_int<std::runtime_error, 2, 3, 4>(dof, who, ": dof must be 2/3/4", f);
+}
+
+template <typename F>
+static inline void dispatch_k(int k, const char* who, F&& f) {
+    dispatch_int<std::invalid_argument, 2, 4, 8>(k, who, ": K must be 2, 4 or 8", f);
+}
+
+// f(type_tag<T1>) if v else f(type_tag<T0>)
+template <typename T1, typename T0, typename F>
+static inline void dispatch_type(bool v, F&& f) {
+    if (v) f(type_tag<T1>{}); else f(type_tag<T0>{});
+}
+
+// col64 / idx64 flag -> long / int indices
+template <typename F>
+static inline void dispatch_index(int is64, F&& f) {
+    dispatch_type<long, int>(is64 != 0, f);
+}
+
+// val32 flag -> fp32- / fp64-stored operator values
+template <typename F>
+static inline void dispatch_value(bool val32, F&& f) {
+    dispatch_type<float, double>(val32, f);
+}
+
+// -- grids --------------------------------------------------------------------
+
+// one wave per 64-row slice, BLOCK/WAVE slices per block; grid-stride
+// takes what MAXG cuts off
+static inline long slice_grid(long nslices) {
+    long blocks = (nslices * WAVE + BLOCK - 1) / BLOCK;
+    if (blocks > MAXG) blocks = MAXG;
+    return blocks;
+}
+
+// Megafused passes write their partials at partials_off + blockIdx.x.  The
+// matA pass (partials_off == 0) must leave partial slots for the matO
+// pass: at >=3.9M rows an uncapped matA claims all MAXG blocks and matO
+// would launch with grid 0 (invalid configuration), so 1024 are reserved.
+static inline long pipe_grid(long blocks, long partials_off) {
+    const long cap = (partials_off == 0) ? (MAXG - 1024) : (MAXG - partials_off);
+    if (blocks > cap) blocks = cap;
+    return blocks;
+}
+
+// block-Jacobi: one thread per node, ~2 nodes per thread before the cap
+static inline long bj_grid(long nnodes) { return elem_grid(nnodes, 2); }
+
+// -- launch -------------------------------------------------------------------
+// Arguments are checked against the kernel's parameter list: a pointer
+// parameter takes a uintptr_t (the only conversion made) or a pointer of
+// exactly its type, any other parameter an argument of exactly its type.
+// An int for a pointer, or a long for an int, does not compile.
+
+template <typename P, typename A>
+static inline P kernel_arg(A a) {
+    if constexpr (std::is_pointer_v<P> && std::is_same_v<A, uintptr_t>) {
+        return reinterpret_cast<P>(a);
+    } else {
+        static_assert(std::is_same_v<P, A>,
+                      "kernel argument: uintptr_t for a pointer, else the exact type");
+        return a;
+    }
+}
+
+template <typename... P, typename... A>
+static inline void launch_cfg(const char* what, void (*kern)(P...), dim3 grid,
+                              dim3 block, size_t lds, uintptr_t stream, A... args) {
+    static_assert(sizeof...(P) == sizeof...(A), "kernel argument count");
+    hipLaunchKernelGGL(kern, grid, block, lds, S(stream), kernel_arg<P>(args)...);
+    check_hip(what);
+}
+
+// the common shape: ``blocks`` x BLOCK threads, no dynamic LDS
+template <typename... P, typename... A>
+static inline void launch(const char* what, void (*kern)(P...), long blocks,
+                          uintptr_t stream, A... args) {
+    launch_cfg(what, kern, dim3((unsigned)blocks), dim3(BLOCK), 0, stream, args...);
+}
+
 static void reduce_partials(uintptr_t partials, int nblocks, uintptr_t scal,
                             int slot, bool accumulate, uintptr_t stream) {
-    hipLaunchKernelGGL(k_reduce_partials, dim3(1), dim3(BLOCK), 0, S(stream),
-                       (const double*)partials, nblocks, (double*)scal, slot,
-                       accumulate ? 1 : 0);
-    check_hip("reduce_partials");
+    launch("reduce_partials", k_reduce_partials, 1, stream, partials, nblocks,
+           scal, slot, accumulate ? 1 : 0);
 }
+
+// -- CSR / SELL SpMV ----------------------------------------------------------
 
 void spmv(long nrows, long rowbase, uintptr_t rowptr, uintptr_t colidx,
           int col64, uintptr_t vals, uintptr_t x, uintptr_t y,
@@ -3004,27 +2831,18 @@ void spmv(long nrows, long rowbase, uintptr_t rowptr, uintptr_t colidx,
     long blocks = (nrows + rows_per_block - 1) / rows_per_block;
     if (blocks > MAXG) blocks = MAXG;
     const bool fuse = partials != 0 && dotslot >= 0;
-    dim3 g((unsigned)blocks), b(BLOCK);
-    #define LAUNCH_SPMV(CT, L, AC, FD) \
-        hipLaunchKernelGGL((spmv_csr_vector<CT, L, AC, FD>), g, b, 0, S(stream), \
-            nrows, rowbase, (const long*)rowptr, (const CT*)colidx, \
-            (const double*)vals, (const double*)x, (double*)y, (double*)partials)
-    #define DISPATCH_L(CT, AC, FD) \
-        switch (lanes) { \
-            case 4:  LAUNCH_SPMV(CT, 4,  AC, FD); break; \
-            case 8:  LAUNCH_SPMV(CT, 8,  AC, FD); break; \
-            case 16: LAUNCH_SPMV(CT, 16, AC, FD); break; \
-            case 32: LAUNCH_SPMV(CT, 32, AC, FD); break; \
-            case 64: LAUNCH_SPMV(CT, 64, AC, FD); break; \
-            default: throw std::runtime_error("spmv: lanes must be 4/8/16/32/64"); }
-    #define DISPATCH_AC(CT) \
-        if (accum) { if (fuse) { DISPATCH_L(CT, true, true) } else { DISPATCH_L(CT, true, false) } } \
-        else       { if (fuse) { DISPATCH_L(CT, false, true) } else { DISPATCH_L(CT, false, false) } }
-    if (col64) { DISPATCH_AC(long) } else { DISPATCH_AC(int) }
-    #undef DISPATCH_AC
-    #undef DISPATCH_L
-    #undef LAUNCH_SPMV
-    check_hip("spmv");
+    dispatch_index(col64, [&](auto ct) {
+        using CT = typename decltype(ct)::type;
+        dispatch_int<std::runtime_error, 4, 8, 16, 32, 64>(
+            lanes, "spmv", ": lanes must be 4/8/16/32/64", [&](auto l) {
+                constexpr int L = l;
+                dispatch_bool(accum, fuse, [&](auto ac, auto fd) {
+                    launch("spmv", spmv_csr_vector<CT, L, ac, fd>, blocks, stream,
+                           nrows, rowbase, rowptr, colidx, vals, x, y, partials,
+                           uintptr_t(0));
+                });
+            });
+    });
     if (fuse)
         reduce_partials(partials, (int)blocks, scal, dotslot, dot_accum, stream);
 }
@@ -3053,32 +2871,22 @@ void spmv_binned(long rowbase, uintptr_t rowptr, uintptr_t colidx, int col64,
         // (5 bins x 3072 <= MAXG partials)
         if (poff + blocks > MAXG)
             throw std::runtime_error("spmv_binned: partials overflow");
-        dim3 g((unsigned)blocks), b(BLOCK);
         const int* rl = (const int*)rowlist + start;
         double* pp = (double*)partials + poff;
-        #define LAUNCH_BIN(CT, L, AC, FD) \
-            hipLaunchKernelGGL((spmv_csr_vector<CT, L, AC, FD, true>), g, b, 0, \
-                S(stream), count, rowbase, (const long*)rowptr, \
-                (const CT*)colidx, (const double*)vals, (const double*)x, \
-                (double*)y, pp, rl)
-        #define DISPATCH_BL(CT, AC, FD) \
-            switch (lanes) { \
-                case 4:  LAUNCH_BIN(CT, 4,  AC, FD); break; \
-                case 8:  LAUNCH_BIN(CT, 8,  AC, FD); break; \
-                case 16: LAUNCH_BIN(CT, 16, AC, FD); break; \
-                case 32: LAUNCH_BIN(CT, 32, AC, FD); break; \
-                case 64: LAUNCH_BIN(CT, 64, AC, FD); break; \
-                default: throw std::runtime_error("spmv_binned: lanes 4/8/16/32/64"); }
-        #define DISPATCH_BA(CT) \
-            if (accum) { if (fuse) { DISPATCH_BL(CT, true, true) } else { DISPATCH_BL(CT, true, false) } } \
-            else       { if (fuse) { DISPATCH_BL(CT, false, true) } else { DISPATCH_BL(CT, false, false) } }
-        if (col64) { DISPATCH_BA(long) } else { DISPATCH_BA(int) }
-        #undef DISPATCH_BA
-        #undef DISPATCH_BL
-        #undef LAUNCH_BIN
+        dispatch_index(col64, [&](auto ct) {
+            using CT = typename decltype(ct)::type;
+            dispatch_int<std::runtime_error, 4, 8, 16, 32, 64>(
+                lanes, "spmv_binned", ": lanes 4/8/16/32/64", [&](auto l) {
+                    constexpr int L = l;
+                    dispatch_bool(accum, fuse, [&](auto ac, auto fd) {
+                        launch("spmv_binned", spmv_csr_vector<CT, L, ac, fd, true>,
+                               blocks, stream, count, rowbase, rowptr, colidx,
+                               vals, x, y, pp, rl);
+                    });
+                });
+        });
         if (fuse) poff += blocks;
     }
-    check_hip("spmv_binned");
     if (fuse && poff > 0)
         reduce_partials(partials, (int)poff, scal, dotslot, dot_accum, stream);
 }
@@ -3089,83 +2897,44 @@ void spmv_sell(long nslices, long nrows, long rowbase, uintptr_t sellptr,
                int dotslot, bool dot_accum, int variant, uintptr_t perm,
                bool val32, uintptr_t stream) {
     if (nrows == 0) return;
-    long blocks = (nslices * WAVE + BLOCK - 1) / BLOCK;
-    if (blocks > MAXG) blocks = MAXG;
+    const long blocks = slice_grid(nslices);
     const bool fuse = partials != 0 && dotslot >= 0;
-    dim3 g((unsigned)blocks), b(BLOCK);
-    if (val32) {
-        // fp32-stored values: only the default flavour (NT, no SWZ,
-        // unroll 8), plain or sigma-perm, is instantiated
-        if ((variant & (SELL_NT | SELL_SWZ | SELL_U8)) != (SELL_NT | SELL_U8))
-            throw std::invalid_argument(
-                "spmv_sell: fp32 values support only variant NT|U8");
-        #define LAUNCH_SELL32(CT, AC, FD, PM) \
-            hipLaunchKernelGGL((k_spmv_sell<CT, AC, FD, true, false, 8, PM, float>), \
-                g, b, 0, S(stream), nslices, nrows, rowbase, \
-                (const long*)sellptr, (const CT*)cols, (const float*)vals, \
-                (const double*)x, (double*)y, (double*)partials, (const int*)perm)
-        #define DISP32_PM(CT, AC, FD) \
-            if (perm != 0) { LAUNCH_SELL32(CT, AC, FD, true); } \
-            else { LAUNCH_SELL32(CT, AC, FD, false); }
-        #define DISP32(CT) \
-            if (accum) { if (fuse) { DISP32_PM(CT, true, true) } else { DISP32_PM(CT, true, false) } } \
-            else       { if (fuse) { DISP32_PM(CT, false, true) } else { DISP32_PM(CT, false, false) } }
-        if (col64) { DISP32(long) } else { DISP32(int) }
-        #undef DISP32
-        #undef DISP32_PM
-        #undef LAUNCH_SELL32
-        check_hip("spmv_sell_f32");
-        if (fuse)
-            reduce_partials(partials, (int)blocks, scal, dotslot, dot_accum, stream);
-        return;
-    }
-    if (perm != 0) {
-        // sigma-sorted SELL (irregular rows): fixed NT, no swizzle;
-        // UNROLL honours the U8 variant bit (deeper unroll = more
-        // outstanding x gathers to hide the random-access latency that
-        // dominates this path)
-        #define LAUNCH_PERM_U(CT, AC, FD, U) \
-            hipLaunchKernelGGL((k_spmv_sell<CT, AC, FD, true, false, U, true>), \
-                g, b, 0, S(stream), nslices, nrows, rowbase, \
-                (const long*)sellptr, (const CT*)cols, (const double*)vals, \
-                (const double*)x, (double*)y, (double*)partials, (const int*)perm)
-        #define LAUNCH_PERM(CT, AC, FD) \
-            if (variant & SELL_U8) { LAUNCH_PERM_U(CT, AC, FD, 8); } \
-            else { LAUNCH_PERM_U(CT, AC, FD, 4); }
-        #define DISPP(CT) \
-            if (accum) { if (fuse) { LAUNCH_PERM(CT, true, true); } else { LAUNCH_PERM(CT, true, false); } } \
-            else       { if (fuse) { LAUNCH_PERM(CT, false, true); } else { LAUNCH_PERM(CT, false, false); } }
-        if (col64) { DISPP(long) } else { DISPP(int) }
-        #undef DISPP
-        #undef LAUNCH_PERM
-        #undef LAUNCH_PERM_U
-        check_hip("spmv_sell_perm");
-        if (fuse)
-            reduce_partials(partials, (int)blocks, scal, dotslot, dot_accum, stream);
-        return;
-    }
-    #define LAUNCH_SELL(CT, AC, FD, NT, SWZ, U) \
-        hipLaunchKernelGGL((k_spmv_sell<CT, AC, FD, NT, SWZ, U>), g, b, 0, S(stream), \
-            nslices, nrows, rowbase, (const long*)sellptr, (const CT*)cols, \
-            (const double*)vals, (const double*)x, (double*)y, (double*)partials)
-    #define DISP_V(CT, AC, FD) \
-        switch (variant & (SELL_NT | SELL_SWZ | SELL_U8)) { \
-            case 0:                               LAUNCH_SELL(CT, AC, FD, false, false, 4); break; \
-            case SELL_NT:                         LAUNCH_SELL(CT, AC, FD, true,  false, 4); break; \
-            case SELL_SWZ:                        LAUNCH_SELL(CT, AC, FD, false, true,  4); break; \
-            case SELL_NT | SELL_SWZ:              LAUNCH_SELL(CT, AC, FD, true,  true,  4); break; \
-            case SELL_U8:                         LAUNCH_SELL(CT, AC, FD, false, false, 8); break; \
-            case SELL_U8 | SELL_NT:               LAUNCH_SELL(CT, AC, FD, true,  false, 8); break; \
-            case SELL_U8 | SELL_SWZ:              LAUNCH_SELL(CT, AC, FD, false, true,  8); break; \
-            default:                              LAUNCH_SELL(CT, AC, FD, true,  true,  8); break; }
-    #define DISP2(CT) \
-        if (accum) { if (fuse) { DISP_V(CT, true, true) } else { DISP_V(CT, true, false) } } \
-        else       { if (fuse) { DISP_V(CT, false, true) } else { DISP_V(CT, false, false) } }
-    if (col64) { DISP2(long) } else { DISP2(int) }
-    #undef DISP2
-    #undef DISP_V
-    #undef LAUNCH_SELL
-    check_hip("spmv_sell");
+    const int flavour = variant & (SELL_NT | SELL_SWZ | SELL_U8);
+    if (val32 && flavour != (SELL_NT | SELL_U8))
+        throw std::invalid_argument(
+            "spmv_sell: fp32 values support only variant NT|U8");
+    dispatch_index(col64, [&](auto ct) {
+        using CT = typename decltype(ct)::type;
+        dispatch_bool(accum, fuse, [&](auto ac, auto fd) {
+            constexpr bool AC = ac, FD = fd;
+            auto go = [&](auto kern) {
+                launch("spmv_sell", kern, blocks, stream, nslices, nrows, rowbase,
+                       sellptr, cols, vals, x, y, partials, perm);
+            };
+            if (val32) {
+                // fp32-stored values: only the default flavour (NT, no SWZ,
+                // unroll 8), plain or sigma-perm, is instantiated
+                dispatch_bool(perm != 0, [&](auto pm) {
+                    go(k_spmv_sell<CT, AC, FD, true, false, 8, pm, float>);
+                });
+            } else if (perm != 0) {
+                // sigma-sorted SELL (irregular rows): fixed NT, no swizzle;
+                // UNROLL honours the U8 variant bit (deeper unroll = more
+                // outstanding x gathers to hide the random-access latency
+                // that dominates this path)
+                dispatch_bool((variant & SELL_U8) != 0, [&](auto u8) {
+                    go(k_spmv_sell<CT, AC, FD, true, false, u8 ? 8 : 4, true>);
+                });
+            } else {
+                dispatch_int<std::logic_error, 0, 1, 2, 3, 4, 5, 6, 7>(
+                    flavour, "spmv_sell", ": variant", [&](auto v) {
+                        constexpr int V = v;
+                        go(k_spmv_sell<CT, AC, FD, (V & SELL_NT) != 0,
+                                       (V & SELL_SWZ) != 0, (V & SELL_U8) ? 8 : 4>);
+                    });
+            }
+        });
+    });
     if (fuse)
         reduce_partials(partials, (int)blocks, scal, dotslot, dot_accum, stream);
 }
@@ -3178,55 +2947,18 @@ long spmv2_sell(long nslices, long nrows, uintptr_t sellptr, uintptr_t cols,
                 uintptr_t b, uintptr_t y1, uintptr_t y2, uintptr_t partials,
                 uintptr_t perm, uintptr_t stream) {
     if (nrows == 0 || nslices == 0) return 0;
-    long blocks = (nslices * WAVE + BLOCK - 1) / BLOCK;
-    if (blocks > MAXG) blocks = MAXG;
-    dim3 g((unsigned)blocks), bl(BLOCK);
-    #define LAUNCH_SELL2(CT, RS, FD, PM) \
-        hipLaunchKernelGGL((k_spmv2_sell<CT, RS, FD, PM>), g, bl, 0, S(stream), \
-            nslices, nrows, (const long*)sellptr, (const CT*)cols, \
-            (const double*)vals, (const double*)x1, (const double*)x2, \
-            (const double*)b, (double*)y1, (double*)y2, (double*)partials, \
-            (const int*)perm)
-    #define DISP2_PM(CT, RS, FD) \
-        if (perm != 0) { LAUNCH_SELL2(CT, RS, FD, true); } \
-        else { LAUNCH_SELL2(CT, RS, FD, false); }
-    #define DISP2_RF(CT) \
-        if (b != 0) { if (partials != 0) { DISP2_PM(CT, true, true) } else { DISP2_PM(CT, true, false) } } \
-        else        { if (partials != 0) { DISP2_PM(CT, false, true) } else { DISP2_PM(CT, false, false) } }
-    if (col64) { DISP2_RF(long) } else { DISP2_RF(int) }
-    #undef DISP2_RF
-    #undef DISP2_PM
-    #undef LAUNCH_SELL2
-    check_hip("spmv2_sell");
-    return blocks;
-}
-
-long spmv2_bsell(long nslices, long nnodes, int dof, uintptr_t bptr,
-                 uintptr_t bcol, uintptr_t bvals, uintptr_t x1, uintptr_t x2,
-                 uintptr_t b, uintptr_t y1, uintptr_t y2, uintptr_t partials,
-                 uintptr_t stream) {
-    if (dof < 2 || dof > 4)
-        throw std::runtime_error("spmv2_bsell: dof must be 2/3/4");
-    if (nnodes == 0 || nslices == 0) return 0;
-    long blocks = (nslices * WAVE + BLOCK - 1) / BLOCK;
-    if (blocks > MAXG) blocks = MAXG;
-    dim3 g((unsigned)blocks), bl(BLOCK);
-    #define LBS2(D, RS, FD) \
-        hipLaunchKernelGGL((k_spmv2_bsell<D, RS, FD>), g, bl, 0, S(stream), \
-            nslices, nnodes, (const long*)bptr, (const int*)bcol, \
-            (const double*)bvals, (const double*)x1, (const double*)x2, \
-            (const double*)b, (double*)y1, (double*)y2, (double*)partials)
-    #define DISP_BS2(D) \
-        if (b != 0) { if (partials != 0) { LBS2(D, true, true); } else { LBS2(D, true, false); } } \
-        else        { if (partials != 0) { LBS2(D, false, true); } else { LBS2(D, false, false); } }
-    switch (dof) {
-        case 2: DISP_BS2(2) break;
-        case 3: DISP_BS2(3) break;
-        default: DISP_BS2(4) break;
-    }
-    #undef DISP_BS2
-    #undef LBS2
-    check_hip("spmv2_bsell");
+    const long blocks = slice_grid(nslices);
+    dispatch_index(col64, [&](auto ct) {
+        using CT = typename decltype(ct)::type;
+        dispatch_bool(b != 0, partials != 0, [&](auto rs, auto fd) {
+            constexpr bool RS = rs, FD = fd;
+            dispatch_bool(perm != 0, [&](auto pm) {
+                launch("spmv2_sell", k_spmv2_sell<CT, RS, FD, pm>, blocks, stream,
+                       nslices, nrows, sellptr, cols, vals, x1, x2, b, y1, y2,
+                       partials, perm);
+            });
+        });
+    });
     return blocks;
 }
 
@@ -3236,167 +2968,327 @@ long dot2_slices(long nslices, long nunits, int dof, uintptr_t r, uintptr_t w,
     if (dof < 1 || dof > 4 || (dof > 1 && perm != 0))
         throw std::runtime_error("dot2_slices: dof must be 1..4, perm only with dof 1");
     if (nunits == 0 || nslices == 0) return 0;
-    long blocks = (nslices * WAVE + BLOCK - 1) / BLOCK;
-    if (blocks > MAXG) blocks = MAXG;
-    dim3 g((unsigned)blocks), bl(BLOCK);
-    #define LD2S(D, PM) \
-        hipLaunchKernelGGL((k_dot2_slices<D, PM>), g, bl, 0, S(stream), nslices, \
-            nunits, (const double*)r, (const double*)w, (const int*)perm, \
-            (double*)partials)
-    switch (dof) {
-        case 1: if (perm != 0) { LD2S(1, true); } else { LD2S(1, false); } break;
-        case 2: LD2S(2, false); break;
-        case 3: LD2S(3, false); break;
-        default: LD2S(4, false); break;
-    }
-    #undef LD2S
-    check_hip("dot2_slices");
+    const long blocks = slice_grid(nslices);
+    auto go = [&](auto kern) {
+        launch("dot2_slices", kern, blocks, stream, nslices, nunits, r, w, perm,
+               partials);
+    };
+    dispatch_int<std::runtime_error, 1, 2, 3, 4>(
+        dof, "dot2_slices", ": dof must be 1..4", [&](auto d) {
+            if constexpr (d == 1)
+                dispatch_bool(perm != 0, [&](auto pm) { go(k_dot2_slices<1, pm>); });
+            else
+                go(k_dot2_slices<d, false>);
+        });
     return blocks;
 }
 
-void pipelined_replace_finalize(uintptr_t partials, int nblocks, uintptr_t scal,
-                                uintptr_t stream) {
-    hipLaunchKernelGGL(k_pipelined_replace_finalize, dim3(1), dim3(BLOCK), 0,
-                       S(stream), (const double*)partials, nblocks, (double*)scal);
-    check_hip("pipelined_replace_finalize");
+// -- Block-SELL ---------------------------------------------------------------
+
+void spmv_bsell(long nslices, long nnodes, int dof, uintptr_t bptr,
+                uintptr_t bcol, uintptr_t bvals, uintptr_t x, uintptr_t y,
+                uintptr_t partials, uintptr_t scal, int dotslot,
+                bool dot_accum, bool val32, uintptr_t stream) {
+    if (nnodes == 0) return;
+    const long blocks = slice_grid(nslices);
+    const bool fuse = partials != 0 && dotslot >= 0;
+    // fp32-stored values keep the same pair-major element order
+    dispatch_value(val32, [&](auto vt) {
+        using VT = typename decltype(vt)::type;
+        dispatch_dof(dof, "spmv_bsell", [&](auto d) {
+            constexpr int D = d;
+            dispatch_bool(fuse, [&](auto fd) {
+                launch("spmv_bsell", k_spmv_bsell<D, fd, VT>, blocks, stream,
+                       nslices, nnodes, bptr, bcol, bvals, x, y, partials);
+            });
+        });
+    });
+    if (fuse)
+        reduce_partials(partials, (int)blocks, scal, dotslot, dot_accum, stream);
 }
 
-void zero_scalars(uintptr_t scal, int i0, int count, uintptr_t stream) {
-    hipLaunchKernelGGL(k_zero_scalars, dim3(1), dim3(BLOCK), 0, S(stream),
-                       (double*)scal, i0, count);
-    check_hip("zero_scalars");
+// Returns the number of blocks launched (= partials written when fused).
+// ``max_blocks`` > 0 caps the grid (grid-stride over tiles takes the rest).
+long spmv_bsell_st(long ntiles, long nslices, long nnodes, int dof, int qmax,
+                   uintptr_t sptr, uintptr_t spl, uintptr_t scol, uintptr_t sq,
+                   uintptr_t svals, uintptr_t nrecv, uintptr_t x, uintptr_t y,
+                   uintptr_t partials, uintptr_t scal, int dotslot,
+                   bool dot_accum, long max_blocks, uintptr_t stream) {
+    if (nnodes == 0 || ntiles == 0) return 0;
+    if (ntiles != (nslices + BLOCK / WAVE - 1) / (BLOCK / WAVE)
+        || nslices != (nnodes + WAVE - 1) / WAVE)
+        throw std::invalid_argument("spmv_bsell_st: tile/slice/node counts disagree");
+    if (qmax < 0 || qmax >= ST_NOSEND)
+        throw std::invalid_argument("spmv_bsell_st: qmax must be in [0, 255)");
+    const size_t lds = (size_t)qmax * dof * BLOCK * sizeof(double);
+    if (lds > 96 * 1024)
+        throw std::invalid_argument("spmv_bsell_st: qmax * dof needs more than 96 KiB of LDS");
+    long blocks = ntiles;
+    if (blocks > MAXG) blocks = MAXG;
+    if (max_blocks > 0 && blocks > max_blocks) blocks = max_blocks;
+    const bool fuse = partials != 0 && dotslot >= 0;
+    dispatch_dof(dof, "spmv_bsell_st", [&](auto d) {
+        constexpr int D = d;
+        dispatch_bool(fuse, [&](auto fd) {
+            auto kern = k_spmv_bsell_st<D, fd>;
+            if (lds > 48 * 1024 && hipFuncSetAttribute(
+                    (const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize,
+                    (int)lds) != hipSuccess)
+                throw std::runtime_error("spmv_bsell_st: cannot raise the LDS limit");
+            launch_cfg("spmv_bsell_st", kern, dim3((unsigned)blocks), dim3(BLOCK),
+                       lds, stream, ntiles, nslices, nnodes, sptr, spl, scol, sq,
+                       svals, nrecv, x, y, partials);
+        });
+    });
+    if (fuse)
+        reduce_partials(partials, (int)blocks, scal, dotslot, dot_accum, stream);
+    return blocks;
 }
 
-void cg_prep_pt(uintptr_t scal, uintptr_t stream) {
-    hipLaunchKernelGGL(k_cg_prep_pt, dim3(1), dim3(64), 0, S(stream), (double*)scal);
-    check_hip("cg_prep_pt");
+void spmv_bsell_daypx(long nslices, long nnodes, int dof, uintptr_t bptr,
+                      uintptr_t bcol, uintptr_t bvals, uintptr_t pold,
+                      uintptr_t rvec, uintptr_t pnew, uintptr_t y,
+                      uintptr_t scal, uintptr_t partials, int dotslot,
+                      uintptr_t stream) {
+    if (nnodes == 0) return;
+    const long blocks = slice_grid(nslices);
+    dispatch_dof(dof, "spmv_bsell_daypx", [&](auto d) {
+        launch("spmv_bsell_daypx", k_spmv_bsell_daypx<d>, blocks, stream, nslices,
+               nnodes, bptr, bcol, bvals, pold, rvec, pnew, y, scal, partials);
+    });
+    reduce_partials(partials, (int)blocks, scal, dotslot, false, stream);
 }
 
-void cg_prep_rr(uintptr_t scal, uintptr_t stream) {
-    hipLaunchKernelGGL(k_cg_prep_rr, dim3(1), dim3(64), 0, S(stream), (double*)scal);
-    check_hip("cg_prep_rr");
-}
-
-void dot(uintptr_t x, uintptr_t y, long n, uintptr_t partials, uintptr_t scal,
-         int slot, bool accumulate, uintptr_t stream) {
-    long blocks = elem_grid(n);
-    hipLaunchKernelGGL(k_dot, dim3((unsigned)blocks), dim3(BLOCK), 0, S(stream),
-                       (const double*)x, (const double*)y, n, (double*)partials);
-    check_hip("dot");
-    reduce_partials(partials, (int)blocks, scal, slot, accumulate, stream);
-}
-
-void dot2(uintptr_t r, uintptr_t w, long n, uintptr_t partials, uintptr_t scal,
-          bool accumulate, uintptr_t stream) {
-    long blocks = elem_grid(n);
-    hipLaunchKernelGGL(k_dot2, dim3((unsigned)blocks), dim3(BLOCK), 0, S(stream),
-                       (const double*)r, (const double*)w, n, (double*)partials);
-    check_hip("dot2");
-    hipLaunchKernelGGL(k_reduce_partials2, dim3(1), dim3(BLOCK), 0, S(stream),
-                       (const double*)partials, (int)blocks, (double*)scal,
-                       accumulate ? 1 : 0);
-    check_hip("dot2_reduce");
-}
-
-void axpy_ratio(uintptr_t y, uintptr_t x, long n, uintptr_t scal, int num, int den,
-                double sign, uintptr_t stream) {
-    hipLaunchKernelGGL(k_axpy_ratio, dim3((unsigned)elem_grid(n)), dim3(BLOCK), 0, S(stream),
-                       (double*)y, (const double*)x, n, (const double*)scal, num, den, sign);
-    check_hip("axpy_ratio");
-}
-
-void daypx_ratio(uintptr_t y, uintptr_t x, long n, uintptr_t scal, int num, int den,
+long spmv2_bsell(long nslices, long nnodes, int dof, uintptr_t bptr,
+                 uintptr_t bcol, uintptr_t bvals, uintptr_t x1, uintptr_t x2,
+                 uintptr_t b, uintptr_t y1, uintptr_t y2, uintptr_t partials,
                  uintptr_t stream) {
-    hipLaunchKernelGGL(k_daypx_ratio, dim3((unsigned)elem_grid(n)), dim3(BLOCK), 0, S(stream),
-                       (double*)y, (const double*)x, n, (const double*)scal, num, den);
-    check_hip("daypx_ratio");
+    if (dof < 2 || dof > 4)
+        throw std::runtime_error("spmv2_bsell: dof must be 2/3/4");
+    if (nnodes == 0 || nslices == 0) return 0;
+    const long blocks = slice_grid(nslices);
+    dispatch_dof(dof, "spmv2_bsell", [&](auto d) {
+        constexpr int D = d;
+        dispatch_bool(b != 0, partials != 0, [&](auto rs, auto fd) {
+            launch("spmv2_bsell", k_spmv2_bsell<D, rs, fd>, blocks, stream, nslices,
+                   nnodes, bptr, bcol, bvals, x1, x2, b, y1, y2, partials);
+        });
+    });
+    return blocks;
 }
-
-void pcg_fused_update(uintptr_t r, uintptr_t x, uintptr_t p, uintptr_t t,
-                      uintptr_t z, uintptr_t dinv, long n, uintptr_t scal,
-                      uintptr_t partials, uintptr_t stream) {
-    long blocks = elem_grid(n);
-    hipLaunchKernelGGL(k_pcg_fused_update, dim3((unsigned)blocks), dim3(BLOCK),
-                       0, S(stream), (double*)r, (double*)x, (const double*)p,
-                       (const double*)t, (double*)z, (const double*)dinv,
-                       n, (const double*)scal, (double*)partials);
-    check_hip("pcg_fused_update");
-    hipLaunchKernelGGL(k_pcg_finalize, dim3(1), dim3(BLOCK), 0, S(stream),
-                       (const double*)partials, (int)blocks, (double*)scal);
-    check_hip("pcg_finalize");
-}
-
-// block-Jacobi: one thread per node, ~2 nodes per thread before the cap
-static inline long bj_grid(long nnodes) { return elem_grid(nnodes, 2); }
-
-#define DISPATCH_DOF(dof, WHAT, MACRO) \
-    switch (dof) { \
-        case 2: MACRO(2); break; \
-        case 3: MACRO(3); break; \
-        case 4: MACRO(4); break; \
-        default: throw std::runtime_error(WHAT ": dof must be 2/3/4"); \
-    }
 
 void bsell_diag_inv(long nslices, long nnodes, int dof, uintptr_t bptr,
                     uintptr_t bcol, uintptr_t bvals, uintptr_t minv,
                     uintptr_t status, uintptr_t stream) {
     if (nnodes == 0) return;
-    long blocks = (nslices * WAVE + BLOCK - 1) / BLOCK;
-    if (blocks > MAXG) blocks = MAXG;
-    #define LDI(D) \
-        hipLaunchKernelGGL((k_bsell_diag_inv<D>), dim3((unsigned)blocks), \
-            dim3(BLOCK), 0, S(stream), nslices, nnodes, (const long*)bptr, \
-            (const int*)bcol, (const double*)bvals, (double*)minv, (int*)status)
-    DISPATCH_DOF(dof, "bsell_diag_inv", LDI)
-    #undef LDI
-    check_hip("bsell_diag_inv");
+    const long blocks = slice_grid(nslices);
+    dispatch_dof(dof, "bsell_diag_inv", [&](auto d) {
+        launch("bsell_diag_inv", k_bsell_diag_inv<d>, blocks, stream, nslices,
+               nnodes, bptr, bcol, bvals, minv, status);
+    });
 }
 
 void bjacobi_apply(uintptr_t minv, uintptr_t r, uintptr_t z, long nnodes,
                    int dof, uintptr_t scal, uintptr_t partials,
                    uintptr_t stream) {
-    long blocks = bj_grid(nnodes);
-    #define LBA(D) \
-        hipLaunchKernelGGL((k_bjacobi_apply<D>), dim3((unsigned)blocks), \
-            dim3(BLOCK), 0, S(stream), (const double*)minv, (const double*)r, \
-            (double*)z, nnodes, (double*)partials)
-    DISPATCH_DOF(dof, "bjacobi_apply", LBA)
-    #undef LBA
-    check_hip("bjacobi_apply");
-    hipLaunchKernelGGL(k_pcg_finalize, dim3(1), dim3(BLOCK), 0, S(stream),
-                       (const double*)partials, (int)blocks, (double*)scal);
-    check_hip("bjacobi_apply_finalize");
+    const long blocks = bj_grid(nnodes);
+    dispatch_dof(dof, "bjacobi_apply", [&](auto d) {
+        launch("bjacobi_apply", k_bjacobi_apply<d>, blocks, stream, minv, r, z,
+               nnodes, partials);
+    });
+    launch("bjacobi_apply", k_pcg_finalize, 1, stream, partials, (int)blocks, scal);
 }
 
 void bpcg_fused_update(uintptr_t r, uintptr_t x, uintptr_t p, uintptr_t t,
                        uintptr_t z, uintptr_t minv, long nnodes, int dof,
                        uintptr_t scal, uintptr_t partials, uintptr_t stream) {
-    long blocks = bj_grid(nnodes);
-    #define LBU(D) \
-        hipLaunchKernelGGL((k_bpcg_fused_update<D>), dim3((unsigned)blocks), \
-            dim3(BLOCK), 0, S(stream), (double*)r, (double*)x, \
-            (const double*)p, (const double*)t, (double*)z, \
-            (const double*)minv, nnodes, (const double*)scal, \
-            (double*)partials)
-    DISPATCH_DOF(dof, "bpcg_fused_update", LBU)
-    #undef LBU
-    check_hip("bpcg_fused_update");
-    hipLaunchKernelGGL(k_pcg_finalize, dim3(1), dim3(BLOCK), 0, S(stream),
-                       (const double*)partials, (int)blocks, (double*)scal);
-    check_hip("bpcg_finalize");
+    const long blocks = bj_grid(nnodes);
+    dispatch_dof(dof, "bpcg_fused_update", [&](auto d) {
+        launch("bpcg_fused_update", k_bpcg_fused_update<d>, blocks, stream, r, x,
+               p, t, z, minv, nnodes, scal, partials);
+    });
+    launch("bpcg_fused_update", k_pcg_finalize, 1, stream, partials, (int)blocks,
+           scal);
 }
-#undef DISPATCH_DOF
+
+// -- slab generators ----------------------------------------------------------
+
+void stencil_blocklen(long nnodes, int gx, int gy, int gz, long nown_nodes,
+                      uintptr_t zs_of_plane, uintptr_t pb, uintptr_t offs,
+                      int ksten, uintptr_t blocklen, uintptr_t stream) {
+    launch("stencil_blocklen", k_stencil_blocklen, elem_grid(nnodes), stream,
+           nnodes, gx, gy, gz, nown_nodes, zs_of_plane, pb, offs, ksten, blocklen);
+}
+
+void stencil_bfill(long nnodes, int gx, int gy, int gz, int dof,
+                   long nown_nodes, uintptr_t zs_of_plane, uintptr_t pb,
+                   uintptr_t offs, int ksten, uintptr_t blocks_md,
+                   uintptr_t bptr, uintptr_t bcol, uintptr_t bvals,
+                   uintptr_t stream) {
+    dispatch_dof(dof, "stencil_bfill", [&](auto d) {
+        launch("stencil_bfill", k_stencil_bfill<d>, elem_grid(nnodes), stream,
+               nnodes, gx, gy, gz, nown_nodes, zs_of_plane, pb, offs, ksten,
+               blocks_md, bptr, bcol, bvals);
+    });
+}
+
+void stencil_rowlen(long nrows_nodes, long row0_node, int gx, int gy, int gz,
+                    int dof, long nown_nodes, uintptr_t zs_of_plane,
+                    uintptr_t pb, uintptr_t offs, int ksten, int filter_ghost,
+                    uintptr_t rowlen, uintptr_t stream) {
+    launch("stencil_rowlen", k_stencil_rowlen, elem_grid(nrows_nodes), stream,
+           nrows_nodes, row0_node, gx, gy, gz, dof, nown_nodes, zs_of_plane, pb,
+           offs, ksten, filter_ghost, rowlen);
+}
+
+void stencil_fill(long nrows_nodes, long row0_node, int gx, int gy, int gz,
+                  int dof, long nown_nodes, uintptr_t zs_of_plane,
+                  uintptr_t pb, uintptr_t offs, int ksten, uintptr_t blocks,
+                  int filter_ghost, uintptr_t sellptr, uintptr_t cols,
+                  uintptr_t vals, uintptr_t stream) {
+    const long nrows = nrows_nodes * dof;
+    launch("stencil_fill", k_stencil_fill, elem_grid(nrows), stream, nrows_nodes,
+           row0_node, gx, gy, gz, dof, nown_nodes, zs_of_plane, pb, offs, ksten,
+           blocks, filter_ghost, sellptr, cols, vals);
+}
+
+// -- matrix-free stencils -----------------------------------------------------
+
+void stencil_spmv7(long plane_nodes, int gx, int z0, int z1, int gz,
+                   long nown_nodes, uintptr_t pb, double diag,
+                   double wxm, double wxp, double wym, double wyp,
+                   double wzm, double wzp, uintptr_t x, uintptr_t y,
+                   uintptr_t partials, uintptr_t scal, int dotslot,
+                   bool dot_accum, uintptr_t stream) {
+    if (plane_nodes == 0 || z1 <= z0) return;
+    long blocks = (plane_nodes + BLOCK - 1) / BLOCK;
+    if (blocks > MAXG) blocks = MAXG;
+    const bool fuse = partials != 0 && dotslot >= 0;
+    dispatch_bool(fuse, [&](auto fd) {
+        launch("stencil_spmv7", k_stencil_spmv7<fd>, blocks, stream, plane_nodes,
+               gx, z0, z1, gz, nown_nodes, pb, diag, wxm, wxp, wym, wyp, wzm, wzp,
+               x, y, partials);
+    });
+    if (fuse)
+        reduce_partials(partials, (int)blocks, scal, dotslot, dot_accum, stream);
+}
+
+long stencil_pipe7(long plane_nodes, int gx, int z0, int z1, int gz,
+                   long border_base, long nown_nodes, uintptr_t pb,
+                   double diag, double wxm, double wxp, double wym,
+                   double wyp, double wzm, double wzp, uintptr_t w_old,
+                   uintptr_t qpart, uintptr_t z, uintptr_t t, uintptr_t p,
+                   uintptr_t xv, uintptr_t r, uintptr_t w_new, uintptr_t scal,
+                   int first, uintptr_t partials, long partials_off,
+                   uintptr_t stream) {
+    if (plane_nodes == 0 || z1 <= z0) return 0;
+    const long blocks = pipe_grid((plane_nodes + BLOCK - 1) / BLOCK, partials_off);
+    launch("stencil_pipe7", k_stencil_pipe7, blocks, stream, plane_nodes, gx, z0,
+           z1, gz, border_base, nown_nodes, pb, diag, wxm, wxp, wym, wyp, wzm, wzp,
+           w_old, qpart, z, t, p, xv, r, w_new, scal, first, partials,
+           partials_off);
+    return blocks;
+}
+
+void stencil_spmv(long nrows_nodes, long row0_node, int gx, int gy, int gz,
+                  long nown_nodes, uintptr_t zs_of_plane, uintptr_t pb,
+                  uintptr_t offs, int ksten, double diag, uintptr_t x,
+                  uintptr_t y, bool mato, uintptr_t partials, uintptr_t scal,
+                  int dotslot, bool dot_accum, uintptr_t stream) {
+    if (nrows_nodes == 0) return;
+    const long blocks = elem_grid(nrows_nodes);
+    const bool fuse = partials != 0 && dotslot >= 0;
+    dispatch_bool(mato, fuse, [&](auto mo, auto fd) {
+        launch("stencil_spmv", k_stencil_spmv<mo, fd>, blocks, stream, nrows_nodes,
+               row0_node, gx, gy, gz, nown_nodes, zs_of_plane, pb, offs, ksten,
+               diag, x, y, partials);
+    });
+    if (fuse)
+        reduce_partials(partials, (int)blocks, scal, dotslot, dot_accum, stream);
+}
+
+long stencil_pipe(long nrows_nodes, long row0_node, long border_base,
+                  int gx, int gy, int gz, long nown_nodes,
+                  uintptr_t zs_of_plane, uintptr_t pb, uintptr_t offs,
+                  int ksten, double diag, uintptr_t w_old, uintptr_t qpart,
+                  uintptr_t z, uintptr_t t, uintptr_t p, uintptr_t xv,
+                  uintptr_t r, uintptr_t w_new, uintptr_t scal, int first,
+                  uintptr_t partials, long partials_off, bool mato,
+                  uintptr_t stream) {
+    if (nrows_nodes == 0) return 0;
+    const long blocks = pipe_grid(elem_grid(nrows_nodes), partials_off);
+    dispatch_bool(mato, [&](auto mo) {
+        launch("stencil_pipe", k_stencil_pipe<mo>, blocks, stream, nrows_nodes,
+               row0_node, border_base, gx, gy, gz, nown_nodes, zs_of_plane, pb,
+               offs, ksten, diag, w_old, qpart, z, t, p, xv, r, w_new, scal, first,
+               partials, partials_off);
+    });
+    return blocks;
+}
+
+// -- scalars, dots and the fused CG updates -----------------------------------
+
+void pipelined_replace_finalize(uintptr_t partials, int nblocks, uintptr_t scal,
+                                uintptr_t stream) {
+    launch("pipelined_replace_finalize", k_pipelined_replace_finalize, 1, stream,
+           partials, nblocks, scal);
+}
+
+void zero_scalars(uintptr_t scal, int i0, int count, uintptr_t stream) {
+    launch("zero_scalars", k_zero_scalars, 1, stream, scal, i0, count);
+}
+
+void cg_prep_pt(uintptr_t scal, uintptr_t stream) {
+    launch_cfg("cg_prep_pt", k_cg_prep_pt, dim3(1), dim3(64), 0, stream, scal);
+}
+
+void cg_prep_rr(uintptr_t scal, uintptr_t stream) {
+    launch_cfg("cg_prep_rr", k_cg_prep_rr, dim3(1), dim3(64), 0, stream, scal);
+}
+
+void dot(uintptr_t x, uintptr_t y, long n, uintptr_t partials, uintptr_t scal,
+         int slot, bool accumulate, uintptr_t stream) {
+    const long blocks = elem_grid(n);
+    launch("dot", k_dot, blocks, stream, x, y, n, partials);
+    reduce_partials(partials, (int)blocks, scal, slot, accumulate, stream);
+}
+
+void dot2(uintptr_t r, uintptr_t w, long n, uintptr_t partials, uintptr_t scal,
+          bool accumulate, uintptr_t stream) {
+    const long blocks = elem_grid(n);
+    launch("dot2", k_dot2, blocks, stream, r, w, n, partials);
+    launch("dot2", k_reduce_partials2, 1, stream, partials, (int)blocks, scal,
+           accumulate ? 1 : 0);
+}
+
+void axpy_ratio(uintptr_t y, uintptr_t x, long n, uintptr_t scal, int num, int den,
+                double sign, uintptr_t stream) {
+    launch("axpy_ratio", k_axpy_ratio, elem_grid(n), stream, y, x, n, scal, num,
+           den, sign);
+}
+
+void daypx_ratio(uintptr_t y, uintptr_t x, long n, uintptr_t scal, int num, int den,
+                 uintptr_t stream) {
+    launch("daypx_ratio", k_daypx_ratio, elem_grid(n), stream, y, x, n, scal, num,
+           den);
+}
+
+void pcg_fused_update(uintptr_t r, uintptr_t x, uintptr_t p, uintptr_t t,
+                      uintptr_t z, uintptr_t dinv, long n, uintptr_t scal,
+                      uintptr_t partials, uintptr_t stream) {
+    const long blocks = elem_grid(n);
+    launch("pcg_fused_update", k_pcg_fused_update, blocks, stream, r, x, p, t, z,
+           dinv, n, scal, partials);
+    launch("pcg_fused_update", k_pcg_finalize, 1, stream, partials, (int)blocks,
+           scal);
+}
 
 void cg_fused_update(uintptr_t r, uintptr_t x, uintptr_t p, uintptr_t t, long n,
                      uintptr_t scal, uintptr_t partials, uintptr_t stream) {
-    long blocks = elem_grid(n);
-    hipLaunchKernelGGL(k_cg_fused_update, dim3((unsigned)blocks), dim3(BLOCK), 0, S(stream),
-                       (double*)r, (double*)x, (const double*)p, (const double*)t,
-                       n, (const double*)scal, (double*)partials);
-    check_hip("cg_fused_update");
-    hipLaunchKernelGGL(k_cg_finalize, dim3(1), dim3(BLOCK), 0, S(stream),
-                       (const double*)partials, (int)blocks, (double*)scal);
-    check_hip("cg_finalize");
+    const long blocks = elem_grid(n);
+    launch("cg_fused_update", k_cg_fused_update, blocks, stream, r, x, p, t, n,
+           scal, partials);
+    launch("cg_fused_update", k_cg_finalize, 1, stream, partials, (int)blocks, scal);
 }
 
 long sell_pipe(long nslices, long nrows_pass, long rowbase, long border_base,
@@ -3406,51 +3298,30 @@ long sell_pipe(long nslices, long nrows_pass, long rowbase, long border_base,
                uintptr_t scal, int first, uintptr_t partials,
                long partials_off, bool mato, uintptr_t stream) {
     if (nrows_pass == 0) return 0;
-    long blocks = (nslices * WAVE + BLOCK - 1) / BLOCK;
-    // the matA pass (partials_off == 0) must leave partial slots for the
-    // matO pass: at >=3.9M rows an uncapped matA claims all MAXG blocks
-    // and matO would launch with grid 0 (invalid configuration)
-    const long cap = (partials_off == 0) ? (MAXG - 1024) : (MAXG - partials_off);
-    if (blocks > cap) blocks = cap;
-    dim3 g((unsigned)blocks), b(BLOCK);
-    #define LP(MATO) \
-        hipLaunchKernelGGL((k_sell_pipe<int, true, 8, MATO>), g, b, 0, S(stream), \
-            nslices, nrows_pass, rowbase, border_base, (const long*)sellptr, \
-            (const int*)cols, (const double*)vals, (const double*)w_old, \
-            (double*)qpart, (double*)z, (double*)t, (double*)p, (double*)x, \
-            (double*)r, (double*)w_new, (const double*)scal, first, \
-            (double*)partials, partials_off)
-    if (mato) { LP(true); } else { LP(false); }
-    #undef LP
-    check_hip("sell_pipe");
+    const long blocks = pipe_grid((nslices * WAVE + BLOCK - 1) / BLOCK, partials_off);
+    dispatch_bool(mato, [&](auto mo) {
+        launch("sell_pipe", k_sell_pipe<int, true, 8, mo>, blocks, stream, nslices,
+               nrows_pass, rowbase, border_base, sellptr, cols, vals, w_old, qpart,
+               z, t, p, x, r, w_new, scal, first, partials, partials_off);
+    });
     return blocks;
 }
 
 void pipelined_finalize(uintptr_t partials, int nblocks, uintptr_t scal, int first,
                         uintptr_t stream) {
-    hipLaunchKernelGGL(k_pipelined_finalize, dim3(1), dim3(BLOCK), 0, S(stream),
-                       (const double*)partials, nblocks, (double*)scal, first);
-    check_hip("pipelined_finalize");
+    launch("pipelined_finalize", k_pipelined_finalize, 1, stream, partials, nblocks,
+           scal, first);
 }
 
 void pipelined_fused(uintptr_t z, uintptr_t t, uintptr_t p, uintptr_t x, uintptr_t r,
                      uintptr_t w, uintptr_t q, long n, uintptr_t scal, int first,
                      uintptr_t partials, bool nt_update, uintptr_t stream) {
-    long blocks = elem_grid(n);
-    if (nt_update)
-        hipLaunchKernelGGL(k_pipelined_fused<true>, dim3((unsigned)blocks), dim3(BLOCK), 0, S(stream),
-                           (double*)z, (double*)t, (double*)p, (double*)x, (double*)r,
-                           (double*)w, (const double*)q, n, (const double*)scal, first,
-                           (double*)partials);
-    else
-        hipLaunchKernelGGL(k_pipelined_fused<false>, dim3((unsigned)blocks), dim3(BLOCK), 0, S(stream),
-                           (double*)z, (double*)t, (double*)p, (double*)x, (double*)r,
-                           (double*)w, (const double*)q, n, (const double*)scal, first,
-                           (double*)partials);
-    check_hip("pipelined_fused");
-    hipLaunchKernelGGL(k_pipelined_finalize, dim3(1), dim3(BLOCK), 0, S(stream),
-                       (const double*)partials, (int)blocks, (double*)scal, first);
-    check_hip("pipelined_finalize");
+    const long blocks = elem_grid(n);
+    dispatch_bool(nt_update, [&](auto ntu) {
+        launch("pipelined_fused", k_pipelined_fused<ntu>, blocks, stream, z, t, p,
+               x, r, w, q, n, scal, first, partials);
+    });
+    pipelined_finalize(partials, (int)blocks, scal, first, stream);
 }
 
 // cooperative launch of the monolithic device CG (reference
@@ -3509,44 +3380,29 @@ int cg_device(long nslices, long nrows, uintptr_t sellptr, uintptr_t cols,
 
 void atomic_probe(uintptr_t y, uintptr_t idx, uintptr_t v, long nnz,
                   int mode, uintptr_t stream) {
-    const long blocks = elem_grid(nnz, 8);
-    hipLaunchKernelGGL(k_atomic_probe, dim3((unsigned)blocks), dim3(BLOCK), 0,
-                       S(stream), (double*)y, (const int*)idx,
-                       (const double*)v, nnz, mode);
-    check_hip("atomic_probe");
+    launch("atomic_probe", k_atomic_probe, elem_grid(nnz, 8), stream, y, idx, v,
+           nnz, mode);
 }
 
 void pack_gather(uintptr_t sendbuf, uintptr_t x, uintptr_t idx, int idx64, long n,
                  uintptr_t stream) {
     if (n == 0) return;
-    dim3 g((unsigned)elem_grid(n, 1)), b(BLOCK);
-    if (idx64)
-        hipLaunchKernelGGL(k_pack_gather<long>, g, b, 0, S(stream),
-                           (double*)sendbuf, (const double*)x, (const long*)idx, n);
-    else
-        hipLaunchKernelGGL(k_pack_gather<int>, g, b, 0, S(stream),
-                           (double*)sendbuf, (const double*)x, (const int*)idx, n);
-    check_hip("pack_gather");
+    dispatch_index(idx64, [&](auto it) {
+        using IT = typename decltype(it)::type;
+        launch("pack_gather", k_pack_gather<IT>, elem_grid(n, 1), stream, sendbuf,
+               x, idx, n);
+    });
 }
 
 // -- multiple right-hand sides ------------------------------------------------
-
-#define DISPATCH_K(k, WHAT, MACRO) \
-    switch (k) { \
-        case 2: MACRO(2); break; \
-        case 4: MACRO(4); break; \
-        case 8: MACRO(8); break; \
-        default: throw std::invalid_argument(WHAT ": K must be 2, 4 or 8"); }
 
 void reduce_partials_multi(uintptr_t partials, int nblocks, int k, uintptr_t scal,
                            int slot, bool accumulate, uintptr_t stream) {
     if (k < 1 || k > 8) throw std::invalid_argument("reduce_partials_multi: K must be 1..8");
     if (nblocks < 0 || nblocks > MAXG || slot < 0 || slot >= S_NSLOTS)
         throw std::invalid_argument("reduce_partials_multi: nblocks/slot out of range");
-    hipLaunchKernelGGL(k_reduce_partials_multi, dim3((unsigned)k), dim3(BLOCK), 0,
-                       S(stream), (const double*)partials, nblocks, (double*)scal,
-                       slot, accumulate ? 1 : 0);
-    check_hip("reduce_partials_multi");
+    launch("reduce_partials_multi", k_reduce_partials_multi, k, stream, partials,
+           nblocks, scal, slot, accumulate ? 1 : 0);
 }
 
 long spmm_sell(long nslices, long nrows, int k, uintptr_t sellptr, uintptr_t cols,
@@ -3554,25 +3410,18 @@ long spmm_sell(long nslices, long nrows, int k, uintptr_t sellptr, uintptr_t col
                uintptr_t partials, uintptr_t scal, int dotslot, bool dot_accum,
                uintptr_t perm, uintptr_t stream) {
     if (nrows == 0 || nslices == 0) return 0;
-    long blocks = (nslices * WAVE + BLOCK - 1) / BLOCK;
-    if (blocks > MAXG) blocks = MAXG;
+    const long blocks = slice_grid(nslices);
     const bool fuse = partials != 0 && dotslot >= 0;
-    dim3 g((unsigned)blocks), b(BLOCK);
-    #define LAUNCH_SPMM(CT, KK, FD, PM) \
-        hipLaunchKernelGGL((k_spmm_sell<CT, KK, FD, PM>), g, b, 0, S(stream), \
-            nslices, nrows, (const long*)sellptr, (const CT*)cols, \
-            (const double*)vals, (const double*)X, (double*)Y, \
-            (double*)partials, (const int*)perm)
-    #define SPMM_PM(CT, KK, FD) \
-        if (perm != 0) { LAUNCH_SPMM(CT, KK, FD, true); } else { LAUNCH_SPMM(CT, KK, FD, false); }
-    #define SPMM_K(KK) \
-        if (col64) { if (fuse) { SPMM_PM(long, KK, true) } else { SPMM_PM(long, KK, false) } } \
-        else       { if (fuse) { SPMM_PM(int, KK, true) } else { SPMM_PM(int, KK, false) } }
-    DISPATCH_K(k, "spmm_sell", SPMM_K)
-    #undef SPMM_K
-    #undef SPMM_PM
-    #undef LAUNCH_SPMM
-    check_hip("spmm_sell");
+    dispatch_k(k, "spmm_sell", [&](auto kk) {
+        constexpr int KK = kk;
+        dispatch_index(col64, [&](auto ct) {
+            using CT = typename decltype(ct)::type;
+            dispatch_bool(fuse, perm != 0, [&](auto fd, auto pm) {
+                launch("spmm_sell", k_spmm_sell<CT, KK, fd, pm>, blocks, stream,
+                       nslices, nrows, sellptr, cols, vals, X, Y, partials, perm);
+            });
+        });
+    });
     if (fuse)
         reduce_partials_multi(partials, (int)blocks, k, scal, dotslot, dot_accum, stream);
     return blocks;
@@ -3591,23 +3440,18 @@ long spmm_bsell(long nslices, long nnodes, int dof, int k, uintptr_t bptr,
     if (!spmm_bsell_supported(dof, k))
         throw std::invalid_argument("spmm_bsell: dof must be 2/3/4 and K 2/4/8");
     if (nnodes == 0 || nslices == 0) return 0;
-    long blocks = (nslices * WAVE + BLOCK - 1) / BLOCK;
-    if (blocks > MAXG) blocks = MAXG;
+    const long blocks = slice_grid(nslices);
     const bool fuse = partials != 0 && dotslot >= 0;
-    dim3 g((unsigned)blocks), b(BLOCK);
-    #define LAUNCH_BSPMM(D, KK, FD) \
-        hipLaunchKernelGGL((k_spmm_bsell<D, KK, FD>), g, b, 0, S(stream), \
-            nslices, nnodes, (const long*)bptr, (const int*)bcol, \
-            (const double*)bvals, (const double*)X, (double*)Y, (double*)partials)
-    #define BSPMM_K(KK) \
-        switch (dof) { \
-            case 2: if (fuse) { LAUNCH_BSPMM(2, KK, true); } else { LAUNCH_BSPMM(2, KK, false); } break; \
-            case 3: if (fuse) { LAUNCH_BSPMM(3, KK, true); } else { LAUNCH_BSPMM(3, KK, false); } break; \
-            default: if (fuse) { LAUNCH_BSPMM(4, KK, true); } else { LAUNCH_BSPMM(4, KK, false); } break; }
-    DISPATCH_K(k, "spmm_bsell", BSPMM_K)
-    #undef BSPMM_K
-    #undef LAUNCH_BSPMM
-    check_hip("spmm_bsell");
+    dispatch_k(k, "spmm_bsell", [&](auto kk) {
+        constexpr int KK = kk;
+        dispatch_dof(dof, "spmm_bsell", [&](auto d) {
+            constexpr int D = d;
+            dispatch_bool(fuse, [&](auto fd) {
+                launch("spmm_bsell", k_spmm_bsell<D, KK, fd>, blocks, stream,
+                       nslices, nnodes, bptr, bcol, bvals, X, Y, partials);
+            });
+        });
+    });
     if (fuse)
         reduce_partials_multi(partials, (int)blocks, k, scal, dotslot, dot_accum, stream);
     return blocks;
@@ -3616,13 +3460,10 @@ long spmm_bsell(long nslices, long nnodes, int dof, int k, uintptr_t bptr,
 long dot_multi(uintptr_t X, uintptr_t Y, long n, int k, uintptr_t partials,
                uintptr_t scal, int slot, bool accumulate, uintptr_t stream) {
     const long blocks = elem_grid(n * k / 2, 1);
-    dim3 g((unsigned)blocks), b(BLOCK);
-    #define DOT_K(KK) \
-        hipLaunchKernelGGL(k_dot_multi<KK>, g, b, 0, S(stream), (const double*)X, \
-                           (const double*)Y, n * KK / 2, (double*)partials)
-    DISPATCH_K(k, "dot_multi", DOT_K)
-    #undef DOT_K
-    check_hip("dot_multi");
+    dispatch_k(k, "dot_multi", [&](auto kk) {
+        launch("dot_multi", k_dot_multi<kk>, blocks, stream, X, Y, n * kk / 2,
+               partials);
+    });
     reduce_partials_multi(partials, (int)blocks, k, scal, slot, accumulate, stream);
     return blocks;
 }
@@ -3633,14 +3474,10 @@ long cg_fused_update_multi(uintptr_t R, uintptr_t X, uintptr_t P, uintptr_t T,
                            long n, int k, uintptr_t scal, uintptr_t partials,
                            uintptr_t stream) {
     const long blocks = elem_grid(n * k / 2, 1);
-    dim3 g((unsigned)blocks), b(BLOCK);
-    #define UPD_K(KK) \
-        hipLaunchKernelGGL(k_cg_fused_update_multi<KK>, g, b, 0, S(stream), \
-                           (double*)R, (double*)X, (const double*)P, (const double*)T, \
-                           n * KK / 2, (const double*)scal, (double*)partials)
-    DISPATCH_K(k, "cg_fused_update_multi", UPD_K)
-    #undef UPD_K
-    check_hip("cg_fused_update_multi");
+    dispatch_k(k, "cg_fused_update_multi", [&](auto kk) {
+        launch("cg_fused_update_multi", k_cg_fused_update_multi<kk>, blocks, stream,
+               R, X, P, T, n * kk / 2, scal, partials);
+    });
     return blocks;
 }
 
@@ -3649,23 +3486,19 @@ void cg_finalize_multi(uintptr_t partials, int nblocks, int k, uintptr_t scal,
     if (k < 1 || k > 8) throw std::invalid_argument("cg_finalize_multi: K must be 1..8");
     if (nblocks < 0 || nblocks > MAXG)
         throw std::invalid_argument("cg_finalize_multi: nblocks out of range");
-    hipLaunchKernelGGL(k_cg_finalize_multi, dim3((unsigned)k), dim3(BLOCK), 0,
-                       S(stream), (const double*)partials, nblocks, (double*)scal,
-                       (double*)rr_out);
-    check_hip("cg_finalize_multi");
+    launch("cg_finalize_multi", k_cg_finalize_multi, k, stream, partials, nblocks,
+           scal, rr_out);
 }
 
 void daypx_ratio_multi(uintptr_t P, uintptr_t R, long n, int k, uintptr_t scal,
                        int num, int den, uintptr_t stream) {
     if (num < 0 || num >= S_NSLOTS || den < 0 || den >= S_NSLOTS)
         throw std::invalid_argument("daypx_ratio_multi: slot out of range");
-    dim3 g((unsigned)elem_grid(n * k / 2, 1)), b(BLOCK);
-    #define DAYPX_K(KK) \
-        hipLaunchKernelGGL(k_daypx_ratio_multi<KK>, g, b, 0, S(stream), (double*)P, \
-                           (const double*)R, n * KK / 2, (const double*)scal, num, den)
-    DISPATCH_K(k, "daypx_ratio_multi", DAYPX_K)
-    #undef DAYPX_K
-    check_hip("daypx_ratio_multi");
+    const long blocks = elem_grid(n * k / 2, 1);
+    dispatch_k(k, "daypx_ratio_multi", [&](auto kk) {
+        launch("daypx_ratio_multi", k_daypx_ratio_multi<kk>, blocks, stream, P, R,
+               n * kk / 2, scal, num, den);
+    });
 }
 
 // -- block CG -------------------------------------------------------------------
@@ -3683,59 +3516,44 @@ static void block_check(const char* what, int k, int kg, int nblocks) {
 long gram_multi(uintptr_t X, uintptr_t Y, long n, int k, uintptr_t partials,
                 uintptr_t stream) {
     const long blocks = block_grid(n);
-    dim3 g((unsigned)blocks), b(BLOCK);
-    #define GRAM_K(KK) \
-        hipLaunchKernelGGL(k_gram_multi<KK>, g, b, 0, S(stream), (const double*)X, \
-                           (const double*)Y, n, (double*)partials)
-    DISPATCH_K(k, "gram_multi", GRAM_K)
-    #undef GRAM_K
-    check_hip("gram_multi");
+    dispatch_k(k, "gram_multi", [&](auto kk) {
+        launch("gram_multi", k_gram_multi<kk>, blocks, stream, X, Y, n, partials);
+    });
     return blocks;
 }
 
 long block_update(uintptr_t X, uintptr_t Sm, uintptr_t Q, uintptr_t T, long n, int k,
                   uintptr_t state, uintptr_t partials, uintptr_t stream) {
     const long blocks = block_grid(n);
-    dim3 g((unsigned)blocks), b(BLOCK);
-    #define BUPD_K(KK) \
-        hipLaunchKernelGGL(k_block_update<KK>, g, b, 0, S(stream), (double*)X, \
-                           (const double*)Sm, (double*)Q, (const double*)T, n, \
-                           (const double*)state, (double*)partials)
-    DISPATCH_K(k, "block_update", BUPD_K)
-    #undef BUPD_K
-    check_hip("block_update");
+    dispatch_k(k, "block_update", [&](auto kk) {
+        launch("block_update", k_block_update<kk>, blocks, stream, X, Sm, Q, T, n,
+               state, partials);
+    });
     return blocks;
 }
 
 void block_ortho(uintptr_t Q, uintptr_t Sm, long n, int k, uintptr_t state,
                  uintptr_t stream) {
-    dim3 g((unsigned)block_grid(n)), b(BLOCK);
-    #define BORTHO_K(KK) \
-        hipLaunchKernelGGL(k_block_ortho<KK>, g, b, 0, S(stream), (double*)Q, \
-                           (double*)Sm, n, (const double*)state)
-    DISPATCH_K(k, "block_ortho", BORTHO_K)
-    #undef BORTHO_K
-    check_hip("block_ortho");
+    dispatch_k(k, "block_ortho", [&](auto kk) {
+        launch("block_ortho", k_block_ortho<kk>, block_grid(n), stream, Q, Sm, n,
+               state);
+    });
 }
 
 void block_coef_alpha(uintptr_t partials, int nblocks, uintptr_t state, int k,
                       int kg, int it, uintptr_t stream) {
     block_check("block_coef_alpha", k, kg, nblocks);
-    hipLaunchKernelGGL(k_block_coef_alpha, dim3(1), dim3(BLOCK), 0, S(stream),
-                       (const double*)partials, nblocks, (double*)state, k, kg, it);
-    check_hip("block_coef_alpha");
+    launch("block_coef_alpha", k_block_coef_alpha, 1, stream, partials, nblocks,
+           state, k, kg, it);
 }
 
 void block_coef_beta(uintptr_t partials, int nblocks, uintptr_t state,
                      uintptr_t rr_out, int k, int kg, int it, bool init,
                      uintptr_t stream) {
     block_check("block_coef_beta", k, kg, nblocks);
-    hipLaunchKernelGGL(k_block_coef_beta, dim3(1), dim3(BLOCK), 0, S(stream),
-                       (const double*)partials, nblocks, (double*)state,
-                       (double*)rr_out, k, kg, it, init ? 1 : 0);
-    check_hip("block_coef_beta");
+    launch("block_coef_beta", k_block_coef_beta, 1, stream, partials, nblocks,
+           state, rr_out, k, kg, it, init ? 1 : 0);
 }
-#undef DISPATCH_K
 
 PYBIND11_MODULE(_acg_kernels, m) {
     m.doc() = "acg_amd gfx950 HIP kernels";
@@ -3768,6 +3586,9 @@ PYBIND11_MODULE(_acg_kernels, m) {
     m.def("spmv", &spmv);
     m.def("spmv_binned", &spmv_binned);
     m.def("spmv_sell", &spmv_sell);
+    m.attr("SELL_NT") = SELL_NT;
+    m.attr("SELL_SWZ") = SELL_SWZ;
+    m.attr("SELL_U8") = SELL_U8;
     m.def("spmv2_sell", &spmv2_sell);
     m.def("zero_scalars", &zero_scalars);
     m.def("cg_prep_pt", &cg_prep_pt);
@@ -3789,6 +3610,7 @@ PYBIND11_MODULE(_acg_kernels, m) {
     m.def("pack_gather", &pack_gather);
     m.def("atomic_probe", &atomic_probe);
     m.def("cg_device", &cg_device);
+    m.attr("BAR_STATE_WORDS") = BAR_STATE_WORDS;
     m.def("stencil_rowlen", &stencil_rowlen);
     m.def("stencil_fill", &stencil_fill);
     m.def("spmv_bsell", &spmv_bsell);
@@ -3796,6 +3618,7 @@ PYBIND11_MODULE(_acg_kernels, m) {
     m.def("spmv_bsell_daypx", &spmv_bsell_daypx);
     m.def("spmv_bsell_st", &spmv_bsell_st);
     m.attr("ST_NOSEND") = ST_NOSEND;
+    m.attr("ST_TILE") = BLOCK;  // nodes per BSELL-ST tile = one workgroup
     m.def("stencil_blocklen", &stencil_blocklen);
     m.def("stencil_bfill", &stencil_bfill);
     m.def("stencil_spmv", &stencil_spmv);
@@ -3813,3 +3636,4 @@ PYBIND11_MODULE(_acg_kernels, m) {
     m.attr("S_NSLOTS") = S_NSLOTS;
     m.attr("MAXG") = MAXG;
 }
+

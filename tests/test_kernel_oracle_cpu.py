@@ -231,6 +231,12 @@ def test_every_gpu_op_has_a_reference():
     ops -= {"pick_lanes", "build_row_bins", "build_sellcsr_hybrid"}
     missing = sorted(o for o in ops if not hasattr(torch_ref, o))
     assert not missing, missing
+    try:
+        from acg_amd.ops import gpu_ops
+    except ImportError:  # extension not built on this machine
+        return
+    # torch_ref keeps its own copy so that it imports without the extension
+    assert torch_ref.BAR_STATE_WORDS == gpu_ops.BAR_STATE_WORDS
 
 
 @pytest.mark.parametrize("first", [True, False])

@@ -400,9 +400,8 @@ def main(argv=None) -> int:
             t0 = time.perf_counter()
             solver = CGSolverHIP(S, comm=comm, device=device,
                                  profile=args.profile)
-            fmt = ("Block-SELL" if solver.bsell is not None else
-                   "sigma-SELL" if solver.sell_perm is not None else
-                   "SELL" if solver.sell is not None else "CSR-vector")
+            fmt = {"bsell": "Block-SELL", "sigma": "sigma-SELL",
+                   "sell": "SELL"}.get(solver.opA.name, "CSR-vector")
             log(f"GPU solver init: operator format {fmt} "
                 f"({time.perf_counter() - t0:.2f}s)")
             b = b.to(device)

@@ -64,12 +64,23 @@ def spmv(rowptr, colidx, vals, x, y, *, rowbase: int = 0, accum: bool = False,
 def spmv_binned(rowptr, colidx, vals, rowlist, bins, x, y, *, rowbase: int = 0,
                 accum: bool = False, partials=None, scal=None,
                 dotslot: int = -1, dot_accum: bool = True) -> None:
-    """Row-binned CSR SpMV: ``rowlist``/``bins`` only schedule the rows on
-    the GPU; every row is still computed exactly once."""
+    """Row-binned CSR SpMV: ``bins`` only schedule the rows on the GPU;
+    every row of ``rowlist`` is computed exactly once and no other row (or
+    its share of the dot) is touched -- the hybrid's long-row list."""
     if rowlist.numel() == 0:
         return
-    spmv(rowptr, colidx, vals, x, y, rowbase=rowbase, accum=accum,
-         partials=partials, scal=scal, dotslot=dotslot, dot_accum=dot_accum)
+    nrows = rowptr.numel() - 1
+    if rowlist.numel() == nrows:
+        return spmv(rowptr, colidx, vals, x, y, rowbase=rowbase, accum=accum,
+                    partials=partials, scal=scal, dotslot=dotslot,
+                    dot_accum=dot_accum)
+    ysub = torch.zeros(nrows, dtype=torch.float64, device=x.device)
+    spmv(rowptr, colidx, vals, x, ysub)
+    rl = rowlist.long()
+    y[rowbase + rl] = y[rowbase + rl] + ysub[rl] if accum else ysub[rl]
+    if scal is not None and dotslot >= 0:
+        d = torch.dot(x[rowbase + rl], ysub[rl])
+        scal[dotslot] = scal[dotslot] + d if dot_accum else d
 
 
 def zero_scalars(scal, i0: int = 0, count=None) -> None:

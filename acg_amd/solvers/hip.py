@@ -37,12 +37,7 @@ from ..part.subdomain import LocalSystem
 from .base import (ColumnTolerances, SolveResult, block_results,
                    cg_flops_per_iter, check_multi_shapes, next_multi_k,
                    refine, replacement_flops, solve_multi_by_column)
-
-
-# Whether a solver builds BSELL-ST without being asked (force_format or
-# ACG_BSELL_ST=1); set from the interleaved measurement in
-# profiles/symtile.md.
-BSELL_ST_DEFAULT = True
+from .operator import build_operators
 
 
 class LaggedReadback:
@@ -101,72 +96,21 @@ class CGSolverHIP:
                 else torch.device("cuda", 0)
         self.device = torch.device(device)
         L = local
-
-        def up(a, dtype=None):
-            t = torch.from_numpy(np.ascontiguousarray(a))
-            return t.to(self.device, non_blocking=True)
-
         self.n = L.nowned
         self.nlocal = L.nowned + L.nghost
-        self.sell = None
-        self.sellO = None
-        self.sell_perm = None
-        self.A_rowptr = self.A_colidx = self.A_vals = None
-        self.O_rowptr = self.O_colidx = self.O_vals = None
-        self.lanesA = self.lanesO = lanes or 16
-        self.bsell = None
-        # tile-symmetric BSELL (ops/symtile.py) of the same operator; only
-        # the serial classic solve runs on it, everything else on bsell
-        self.bsell_st = None
-        self.hybrid = None  # (rowlist int32, bins) row-binned CSR
-        # matrix-free analytic operator (dof=1 stencils, opt-in): the SpMV
-        # reads NO matrix data -- see ops/kernels.hip k_stencil_spmv.
-        self.matfree = None
-        if matfree:
-            mf = getattr(L, "mf_tables", None)
-            if mf is None:
-                raise ValueError(
-                    "matfree=True needs a device-generated dof=1 stencil "
-                    "system (gen.device_slab with spec dof==1)")
-            self.matfree = mf
-        if hasattr(L, "A_sell"):
-            # device-generated system (gen.device_slab): SELL already in HBM
-            self.sell = L.A_sell
-            self.sellO = L.O_sell
-            self.bsell = getattr(L, "A_bsell", None)
-            if self.sell is None and self.matfree is None:
-                raise ValueError("system generated with operator=False "
-                                 "requires matfree=True")
-        else:
-            self.A_rowptr = up(L.A_rowptr)
-            self.A_colidx = up(L.A_colidx)
-            self.A_vals = up(L.A_vals)
-            self.O_rowptr = up(L.O_rowptr)
-            self.O_colidx = up(L.O_colidx)
-            self.O_vals = up(L.O_vals)
-            mean_nnz = L.nnzA / max(L.nowned, 1)
-            self.lanesA = lanes or ops.pick_lanes(mean_nnz)
-            mean_nnzO = L.nnzO / max(L.nborder, 1)
-            self.lanesO = lanes or ops.pick_lanes(mean_nnzO)
-            self._pick_format(L, up, use_sell, force_format)
-        # megafused pipelined iteration needs SELL everywhere + int32 cols.
-        # Measured on MI355X: for wide rows (~80 nnz, Queen-shaped) the fused
-        # epilogue's 6 vector streams cost the SpMV more x-gather locality
-        # than the saved q round-trip is worth (815us fused vs 805us split);
-        # for narrow rows (7-pt Poisson) the q elimination is ~8% of the
-        # iteration's traffic.  Auto-enable below ~16 nnz/row.
-        self.can_megafuse = (
-            self.matfree is not None
-            or (self.sell is not None and self.sell_perm is None
-                and self.sell[1].dtype == torch.int32
-                and (L.nnzO == 0 or (self.sellO is not None
-                                     and self.sellO[1].dtype == torch.int32))))
-        # matrix-free: megafusion always pays (the SpMV reads no matrix, so
-        # the vector-traffic saving has no x-gather-locality cost to trade)
-        self.megafuse_auto = (self.can_megafuse
-                              and (self.matfree is not None
-                                   or L.nnzA / max(L.nowned, 1) <= 16.0))
-        self._build_symtile(force_format)
+        # every format-specific tensor and kernel call lives in the operator
+        # module; the solver holds the operators by role (see OperatorSet):
+        # opA / opO are what _spmv_overlapped applies, ``operators.pipe`` and
+        # ``operators.device_cg`` the SELL or stencil operators of the
+        # megafused pass and the one-launch CG (SELL copies where opA is
+        # BSELL)
+        self.operators = build_operators(
+            L, force_format, use_sell, lanes, matfree, self.device,
+            serial=comm is None or comm.size == 1, ops=ops)
+        self.opA, self.opO = self.operators.A, self.operators.O
+        self._opA32 = None  # fp32-stored twin of opA, built by _lowprec_op
+        self.can_megafuse = self.operators.pipe is not None
+        self.megafuse_auto = self.operators.pipe_auto
         self.halo = HaloExchange(L.halo, L.nowned, self.device, comm)
         self.scal = ops.alloc_scalars(self.device)
         self.partials = ops.alloc_partials(self.device)
@@ -191,7 +135,6 @@ class CGSolverHIP:
         self._ws: dict = {}
         self._graphs: dict = {}
         self._nstag = 0
-        self._vals32 = None  # fp32 matA values, built by _lowprec_values
         # solve_multi: columns per SpMM group, 2, 4 or 8.  A group of 8
         # reads the matrix least often; on the 4.1 M-row Queen-shaped
         # system two groups of 4 were nevertheless measured faster than
@@ -201,144 +144,77 @@ class CGSolverHIP:
         # replacement where the dual-SpMV fast path would apply (A/B, tests)
         self._rr_fast = True
 
-    def _pick_format(self, L, up, use_sell: bool, force: str | None) -> None:
-        """Choose the matA operator format (reference analog: the choice
-        between hipsparse ALG_DEFAULT and the hand merge-path kernel,
-        cghip.c:533-585 / cg-kernels-hip.hip:348).
+    # -- the benchmark's interface: bench.py reads these five (and tests and
+    # tools a few more below); everything in this file asks the operators --
 
-        Auto ladder by measured fit:
-          1. plain SELL-C-64 when padding waste <= 0.3 (stencil/FEM rows),
-          2. sigma-SELL (window 16) when waste <= 0.5 (mildly irregular),
-          3. row-binned hybrid CSR otherwise (power-law rows; MEASURED on
-             MI355X 1M-row power-law: hybrid 665 us/it vs single-lane CSR
-             855 vs wide-sigma SELL 2627 -- slice-length imbalance makes
-             wide sigma lose badly, so it is force-only),
-        plus Block-SELL whenever dense dof x dof block structure is found
-        (density >= 0.75) -- it wins on index bytes.
-        ``force`` in {csr, sell, sigma, bsell, hybrid} overrides for A/B
-        measurement (bench --format)."""
-        from ..ops.torch_ref import bsell_from_csr, sell_from_csr
+    @property
+    def matfree(self):
+        return getattr(self.opA, "mf", None)
 
-        if L.nowned == 0:
-            return
+    @property
+    def bsell(self):
+        b = self.operators.bsell
+        return b.arrays if b is not None else None
 
-        def mk_hybrid(cut: int | None = None):
-            """SELL+CSR split (short rows SELL, long tail binned CSR).
-            MEASURED (MI355X 1M-row power-law): the pure binned hybrid's
-            4/8-lane short-row bins cost 400 us/it of its 587 us SpMV --
-            SELL's lockstep 512 B line loads serve those rows instead.
-            Costs ~1.75x operator memory (CSR kept for the long rows).
-            ACG_HYBRID_CUT overrides the split length (tuning sweeps)."""
-            if cut is None:
-                cut = int(os.environ.get("ACG_HYBRID_CUT", "192"))
-            window = int(os.environ.get("ACG_HYBRID_WINDOW", "0"))
-            bucket = int(os.environ.get("ACG_HYBRID_BUCKET", "8"))
-            sp_, cols, svals, perm, rowlist, bins = ops.build_sellcsr_hybrid(
-                L.A_rowptr, L.A_colidx, L.A_vals, cut=cut, window=window,
-                bucket=bucket)
-            self.hybrid = {
-                "sellptr": up(sp_) if sp_ is not None else None,
-                "cols": up(cols) if sp_ is not None else None,
-                "svals": up(svals) if sp_ is not None else None,
-                "perm": up(perm) if sp_ is not None else None,
-                "rowlist": up(rowlist) if len(rowlist) else None,
-                "bins": bins,
-            }
-            if L.nnzO > 0:
-                # matO rows inherit the same power-law tail: bin them too
-                rlO, binsO = ops.build_row_bins(L.O_rowptr)
-                self.hybrid["rowlistO"] = up(rlO)
-                self.hybrid["binsO"] = binsO
+    @property
+    def sell(self):
+        s = self.operators.sell
+        return s.arrays if s is not None else None
 
-        def mk_binned():
-            rowlist, bins = ops.build_row_bins(L.A_rowptr)
-            self.hybrid = {"sellptr": None, "cols": None, "svals": None,
-                           "perm": None, "rowlist": up(rowlist),
-                           "bins": bins}
+    @property
+    def sell_perm(self):
+        s = self.operators.sell
+        return s.perm if s is not None else None
 
-        def mk_sell(sigma):
-            out = sell_from_csr(L.A_rowptr, L.A_colidx, L.A_vals, sigma=sigma)
-            if sigma > 1:
-                sellptr, scols, svals, perm = out
-                self.sell_perm = up(perm)
-            else:
-                sellptr, scols, svals = out
-                self.sell_perm = None
-            self.sell = (up(sellptr), up(scols), up(svals))
-            if L.nnzO > 0:
-                optr, ocols, ovals = sell_from_csr(L.O_rowptr, L.O_colidx,
-                                                   L.O_vals)
-                self.sellO = (up(optr), up(ocols), up(ovals))
-            return (int(sellptr[-1]) - L.nnzA) / max(L.nnzA, 1)
+    @property
+    def hybrid(self):
+        """The hybrid or binned operator as the dict this attribute used to
+        be (None without one): the SELL part's ``sellptr``/``cols``/
+        ``svals``/``perm`` and the binned part's ``rowlist``, each None for
+        an empty part, ``bins``, and ``rowlistO``/``binsO`` where the matO
+        rows were binned too."""
+        h = self.operators.hybrid
+        if h is None:
+            return None
+        sell, binned = getattr(h, "sell", None), getattr(h, "binned", h)
+        sp, sc, sv = sell.arrays if sell is not None else (None,) * 3
+        d = {"sellptr": sp, "cols": sc, "svals": sv,
+             "perm": sell.perm if sell is not None else None,
+             "rowlist": binned.rowlist if binned is not None else None,
+             "bins": binned.bins if binned is not None else []}
+        if self.opO is not None and self.opO.fmt == "binned":
+            d["rowlistO"], d["binsO"] = self.opO.rowlist, self.opO.bins
+        return d
 
-        def mk_bsell():
-            for dof_try in (4, 3, 2):  # kernel dispatch covers 2/3/4
-                out = bsell_from_csr(L.A_rowptr, L.A_colidx, L.A_vals, dof_try)
-                if out is None:
-                    continue
-                bptr_h, bcol_h, bvals_h, density = out
-                if density >= 0.75:
-                    self.bsell = (up(bptr_h), up(bcol_h), up(bvals_h), dof_try)
-                    return True
-            return False
+    @property
+    def sellO(self):
+        s = self.operators.sellO
+        return s.arrays if s is not None else None
 
-        if force == "csr":
-            return
-        if force == "hybrid":
-            mk_hybrid()
-            return
-        if force == "binned":
-            mk_binned()
-            return
-        if force == "sell":
-            mk_sell(1)
-        elif force == "sigma":
-            mk_sell(4096)
-        elif force in ("bsell", "bsell-st"):
-            if not mk_bsell():
-                raise ValueError(f"force_format={force}: no dense dof x dof "
-                                 "block structure (density < 0.75)")
-        elif use_sell:  # auto ladder
-            waste = mk_sell(1)
-            if waste > 0.3:
-                self.sell = self.sellO = self.sell_perm = None
-                waste = mk_sell(16)
-                if waste > 0.5:
-                    self.sell = self.sellO = self.sell_perm = None
-                    mk_hybrid()
-            mk_bsell()
-        if self.sell is not None or self.bsell is not None:
-            self.A_rowptr = self.A_colidx = self.A_vals = None  # free CSR
+    @property
+    def bsell_st(self):
+        """Tile-symmetric BSELL (ops/symtile.py) of the same operator; only
+        the serial classic solve runs on it, everything else on bsell."""
+        return self.opA.st
 
-    def _build_symtile(self, force: str | None) -> None:
-        """Build BSELL-ST next to BSELL where the classic solve can use it:
-        one rank, no matO, a bsell operator, no other format forced.  The
-        builder's own gate (exact transposes inside a tile, padded bytes
-        <= 0.9 of BSELL's) decides; a refusal keeps BSELL, except under
-        ``force_format="bsell-st"``, which raises.  Without the force the
-        format is built when BSELL_ST_DEFAULT or ACG_BSELL_ST=1 says so;
-        ACG_BSELL_ST=0 is the kill switch."""
-        from ..ops.symtile import bsell_st_build
+    @property
+    def _vals32(self):
+        return self._opA32.vals if self._opA32 is not None else None
 
-        env = os.environ.get("ACG_BSELL_ST", "")
-        serial = self.comm is None or self.comm.size == 1
-        wanted = force == "bsell-st" or (
-            force is None and (env == "1" or (BSELL_ST_DEFAULT and env != "0")))
-        if (wanted and env != "0" and serial and self.local.nnzO == 0
-                and self.bsell is not None and self.matfree is None):
-            bptr, bcol, bvals, dof = self.bsell
-            self.bsell_st = bsell_st_build(
-                bptr, bcol, bvals, self.n // dof, dof,
-                getattr(self.local, "node_order", None))
-            if self.bsell_st is not None:
-                print(f"# classic CG operator format: bsell-st "
-                      f"({self.bsell_st.ratio:.3f} of the bsell bytes)",
-                      file=sys.stderr, flush=True)
-        if force == "bsell-st" and self.bsell_st is None:
-            raise ValueError(
-                "force_format=bsell-st: not built (needs one rank, no matO, "
-                "ACG_BSELL_ST != 0, exact transposes inside every tile and "
-                "stored bytes <= 0.9 of BSELL's)")
+    @property
+    def lanesO(self):
+        return self.operators.lanesO
+
+    def _csr_view(self, which: str, i: int):
+        """Array i of the CSR triple ``csrA`` / ``csrO`` still on the
+        device, or None."""
+        csr = getattr(self.operators, which)
+        return csr[i] if csr is not None else None
+
+    A_rowptr = property(lambda self: self._csr_view("csrA", 0))
+    O_rowptr = property(lambda self: self._csr_view("csrO", 0))
+    O_colidx = property(lambda self: self._csr_view("csrO", 1))
+    O_vals = property(lambda self: self._csr_view("csrO", 2))
 
     def _workspace(self, key: str, names) -> dict:
         """Per-method persistent vectors, base-address STAGGERED: equal-size
@@ -431,127 +307,52 @@ class CGSolverHIP:
             return
         from .profiling import annotate_op_stats
 
-        idxb = None
-        if self.matfree is not None:
-            idxb = -8.0  # matrix-free: no vals (8 B) and no cols read
-        elif self.bsell is not None:
-            idxb = 4.0 / (self.bsell[3] ** 2)
         annotate_op_stats(res, self.local, self.prof.collect(),
-                          idx_bytes_per_nnz=idxb)
+                          idx_bytes_per_nnz=self.opA.idx_bytes_per_nnz)
         self.prof.reset()
 
     def _format_name(self) -> str:
-        if self.matfree is not None:
-            return "matrix-free"
-        if hasattr(self.local, "A_sell"):
-            return "device-generated"
-        if self.bsell is not None:
-            return "bsell"  # classic_format says whether solve() takes bsell-st
-        if self.sell is not None:
-            return "sigma" if self.sell_perm is not None else "sell"
-        if self.hybrid is not None:
-            return "hybrid" if self.hybrid["sellptr"] is not None else "binned"
-        return "csr"
+        return self.opA.name
 
     @property
     def classic_format(self) -> str:
         """Operator format of the plain classic solve: "bsell-st" when the
         tile-symmetric operator was built, else :meth:`_format_name`."""
-        return "bsell-st" if self.bsell_st is not None else self._format_name()
+        return "bsell-st" if self.opA.st is not None else self.opA.name
 
-    def _lowprec_values(self) -> torch.Tensor:
-        """fp32 copy of the matA values of the chosen format (plain SELL,
-        sigma-SELL or BSELL), built on first use.  Same element order, so
-        the cast is the whole pack step.  The fp64 values are KEPT --
-        refinement needs the exact residual -- so a solver that uses the
-        fp32 operator holds 1.5x the value memory.  matO stays fp64."""
-        if self._vals32 is None and self.n == 0:  # rank without rows
-            self._vals32 = torch.empty(0, dtype=torch.float32,
-                                       device=self.device)
-        if self._vals32 is None:
-            fmt = self._format_name()
-            if fmt not in ("sell", "sigma", "bsell"):
-                raise ValueError(
-                    f"the fp32-stored operator needs the SELL, sigma-SELL or "
-                    f"BSELL format; this system uses {fmt}")
-            src = self.bsell[2] if self.bsell is not None else self.sell[2]
-            self._vals32 = src.to(torch.float32)
-        return self._vals32
+    def _lowprec_op(self):
+        """opA on fp32-stored values (plain SELL, sigma-SELL or BSELL;
+        ValueError names any other format), built on first use.  The solver
+        then holds 1.5x the value memory.  matO stays fp64."""
+        if self._opA32 is None:
+            self._opA32 = self.opA.fp32()
+        return self._opA32
 
     def _spmv_overlapped(self, xfull: torch.Tensor, y: torch.Tensor,
                          fuse_dotslot: int = -1, lowprec: bool = False):
         """halo(x) on comm stream overlapped with SpMV(matA); SpMV(matO)
         after the ghost tail arrives.  Mirrors reference cghip.c:887-931.
         ``lowprec`` selects the fp32-stored matA values (see
-        _lowprec_values); the default is the fp64 operator."""
-        L = self.local
-        vals32 = self._lowprec_values() if lowprec else None
+        _lowprec_op); the default is the fp64 operator."""
+        opA = self._lowprec_op() if lowprec else self.opA
         have_halo = self.comm is not None and self.comm.size > 1
         if have_halo:
             halo_span = self.prof.span("halo", self.comm_stream)
             self._halo_fork(xfull, halo_span)  # closed after the join below
-        fuse = dict(partials=self.partials,
-                    scal=self.scal if fuse_dotslot >= 0 else None,
-                    dotslot=fuse_dotslot)
+        scal = self.scal if fuse_dotslot >= 0 else None
         with self.prof.span("spmvA"):
             # the matA pass OVERWRITES the dot slot (dot_accum=False), so
             # no zeroing prep kernel is needed; matO accumulates on top
-            if self.matfree is not None:
-                ops.stencil_spmv(self.matfree, self.n, 0, xfull, y,
-                                 mato=False, dot_accum=False, **fuse)
-            elif self.bsell is not None:
-                bptr, bcol, bvals, dof = self.bsell
-                ops.spmv_bsell(bptr, bcol,
-                               bvals if vals32 is None else vals32,
-                               self.n // dof, dof,
-                               xfull, y, dot_accum=False, **fuse)
-            elif self.sell is not None:
-                sellptr, scols, svals = self.sell
-                if vals32 is not None:
-                    svals = vals32
-                ops.spmv_sell(sellptr, scols, svals, self.n, xfull, y,
-                              accum=False, perm=self.sell_perm,
-                              dot_accum=False, **fuse)
-            elif self.hybrid is not None:
-                h = self.hybrid
-                have_sell = h["sellptr"] is not None
-                if have_sell:
-                    ops.spmv_sell(h["sellptr"], h["cols"], h["svals"],
-                                  self.n, xfull, y, accum=False,
-                                  perm=h["perm"], dot_accum=False, **fuse)
-                if h["rowlist"] is not None:
-                    # rows are disjoint from the SELL set: y writes stay
-                    # overwrite-mode; the fused dot ACCUMULATES on top of
-                    # the SELL part's contribution
-                    ops.spmv_binned(self.A_rowptr, self.A_colidx,
-                                    self.A_vals, h["rowlist"], h["bins"],
-                                    xfull, y, accum=False,
-                                    dot_accum=have_sell, **fuse)
-            else:
-                ops.spmv(self.A_rowptr, self.A_colidx, self.A_vals, xfull, y,
-                         lanes=self.lanesA, accum=False, dot_accum=False,
-                         **fuse)
+            opA.apply(xfull, y, accum=False, dot_accum=False,
+                      partials=self.partials, scal=scal, dotslot=fuse_dotslot)
         if have_halo:
             self._halo_join()
             halo_span.__exit__(None, None, None)
-        if L.nborder > 0 and self.local.nnzO > 0:
+        if self.opO is not None:
             with self.prof.span("spmvO"):
-                if self.matfree is not None:
-                    ops.stencil_spmv(self.matfree, L.nborder, L.ninterior,
-                                     xfull, y, mato=True, **fuse)
-                elif self.sellO is not None:
-                    optr, ocols, ovals = self.sellO
-                    ops.spmv_sell(optr, ocols, ovals, L.nborder, xfull, y,
-                                  rowbase=L.ninterior, accum=True, **fuse)
-                elif self.hybrid is not None and "rowlistO" in self.hybrid:
-                    ops.spmv_binned(self.O_rowptr, self.O_colidx, self.O_vals,
-                                    self.hybrid["rowlistO"],
-                                    self.hybrid["binsO"], xfull, y,
-                                    rowbase=L.ninterior, accum=True, **fuse)
-                else:
-                    ops.spmv(self.O_rowptr, self.O_colidx, self.O_vals, xfull, y,
-                             rowbase=L.ninterior, lanes=self.lanesO, accum=True,
-                             **fuse)
+                self.opO.apply(xfull, y, accum=True, dot_accum=True,
+                               partials=self.partials, scal=scal,
+                               dotslot=fuse_dotslot)
 
     def _host_scalar(self, slot: int) -> float:
         cur = torch.cuda.current_stream(self.device)
@@ -622,7 +423,7 @@ class CGSolverHIP:
         # BSELL-ST: the whole solve runs in the operator's permuted node
         # order (b and x gathered once here, x scattered back in
         # _finish_classic); the vector kernels do not care about the order
-        st = self.bsell_st
+        st = self.opA.st
         if lowprec or fold_daypx is True or diff_atol > 0 or diff_rtol > 0:
             st = None
 
@@ -632,9 +433,9 @@ class CGSolverHIP:
                                       lowprec=lowprec)
                 return
             with self.prof.span("spmvA"):
-                S.spmv_bsell_st(st, xv, yv, partials=self.partials,
-                                scal=scal if fuse_dotslot >= 0 else None,
-                                dotslot=fuse_dotslot, dot_accum=False)
+                self.opA.apply_st(xv, yv, partials=self.partials,
+                                  scal=scal if fuse_dotslot >= 0 else None,
+                                  dotslot=fuse_dotslot, dot_accum=False)
 
         if st is None:
             xi.copy_(x)
@@ -679,7 +480,7 @@ class CGSolverHIP:
         # gather footprint (p_old AND r) costs +60 us/it on Queen vs the
         # ~15 us the daypx saves (553.6 vs 493.8 us/it interleaved) --
         # the SpMV gather is the roofline resource, not kernel count.
-        fold = (serial and self.bsell is not None and self.local.nnzO == 0
+        fold = (serial and self.opA.has_daypx and self.local.nnzO == 0
                 and fold_daypx is True)
         if fold:
             p2 = self._workspace("classic", [("p2", True)])["p2"]
@@ -704,12 +505,10 @@ class CGSolverHIP:
 
         def body(k: int = 0):
             if fold:
-                bptr, bcol, bvals, dof = self.bsell
                 pold, pnew = (p, p2) if k % 2 == 0 else (p2, p)
                 with self.prof.span("spmvA"):
-                    S.spmv_bsell_daypx(bptr, bcol, bvals, n // dof, dof,
-                                       pold, r, pnew, t, scal,
-                                       self.partials, S.S_PT)
+                    self.opA.spmv_daypx(pold, r, pnew, t, scal,
+                                        self.partials, S.S_PT)
                 with self.prof.span("update_classic"):
                     S.cg_fused_update(r, xi, pnew, t, scal, self.partials, n)
                 return
@@ -836,9 +635,8 @@ class CGSolverHIP:
         """The SpMM iteration exists for one rank with a SELL, sigma-SELL
         or BSELL matA and no matO; everything else loops over solve()."""
         serial = self.comm is None or self.comm.size == 1
-        return (serial and self.matfree is None and self.local.nnzO == 0
-                and self.n > 0
-                and (self.bsell is not None or self.sell is not None))
+        return (serial and self.opA.has_spmm and self.local.nnzO == 0
+                and self.n > 0)
 
     def _multi_kmax(self) -> int:
         """Largest kernel-level K the operator format offers (a BSELL
@@ -846,10 +644,7 @@ class CGSolverHIP:
         if self.multi_group not in ops.MULTI_K:
             raise ValueError(f"multi_group must be one of {ops.MULTI_K}, "
                              f"got {self.multi_group}")
-        ok = [k for k in ops.MULTI_K if k <= self.multi_group
-              and (self.bsell is None
-                   or ops.spmm_bsell_supported(self.bsell[3], k))]
-        return max(ok) if ok else 0
+        return self.opA.spmm_kmax(self.multi_group)
 
     def solve_multi(self, B: torch.Tensor, X: torch.Tensor, maxits: int = 100,
                     res_atol: float = 0.0, res_rtol: float = 1e-9) -> list:
@@ -891,13 +686,7 @@ class CGSolverHIP:
               dotslot: int = -1) -> None:
         fuse = dict(partials=partials, scal=scal, dotslot=dotslot) \
             if dotslot >= 0 else {}
-        if self.bsell is not None:
-            bptr, bcol, bvals, dof = self.bsell
-            ops.spmm_bsell(bptr, bcol, bvals, self.n // dof, dof, Xm, Y, **fuse)
-        else:
-            sellptr, scols, svals = self.sell
-            ops.spmm_sell(sellptr, scols, svals, self.n, Xm, Y,
-                          perm=self.sell_perm, **fuse)
+        self.opA.spmm(Xm, Y, **fuse)
 
     def _multi_ws(self, kind: str, K: int) -> dict:
         """Persistent (rows, K) buffers of one group width, kept as
@@ -1195,7 +984,7 @@ class CGSolverHIP:
         scaled Queen-shaped system: -15% / -19% time-to-solution at rtol
         1e-9 / 1e-12 against 1e-4's -10% / -13%): a sweep costs 3-4
         iteration equivalents, so few deep sweeps beat many shallow ones."""
-        self._lowprec_values()  # unsupported format: fail before any work
+        self._lowprec_op()  # unsupported format: fail before any work
         res = SolveResult(solver="cg-hip-mixed", maxits=maxits,
                           res_atol=res_atol, res_rtol=res_rtol,
                           nranks=self.comm.size if self.comm else 1)
@@ -1253,7 +1042,8 @@ class CGSolverHIP:
 
             raise AcgError(ErrCode.NOT_SUPPORTED,
                            "device-side CG is single-GPU (reference parity)")
-        if self.sell is None or self.sell_perm is not None:
+        sell = self.operators.device_cg
+        if sell is None:
             from ..utils.errors import AcgError, ErrCode
 
             raise AcgError(ErrCode.NOT_SUPPORTED,
@@ -1267,12 +1057,10 @@ class CGSolverHIP:
         out2 = torch.zeros(2, dtype=torch.int32, device=self.device)
         barrier_state = torch.zeros(ops.BAR_STATE_WORDS, dtype=torch.int32,
                                     device=self.device)
-        sellptr, scols, svals = self.sell
         torch.cuda.synchronize(self.device)
         t0 = time.perf_counter()
-        ops.cg_device(sellptr, scols, svals, n, b, x, r, p, t, self.scal,
-                      self.partials, out2, barrier_state, maxits, res_atol,
-                      res_rtol)
+        sell.cg_device(b, x, r, p, t, self.scal, self.partials, out2,
+                       barrier_state, maxits, res_atol, res_rtol)
         torch.cuda.synchronize(self.device)
         res.tsolve = time.perf_counter() - t0
         S = ops
@@ -1390,22 +1178,8 @@ class CGSolverHIP:
     def _block_inverse(self) -> torch.Tensor:
         """Packed inverse diagonal blocks of the Block-SELL matA, built on
         the GPU once per solver instance (one launch + one status read)."""
-        from ..utils.errors import AcgError, ErrCode
-
-        if self.bsell is None:
-            raise AcgError(ErrCode.NOT_SUPPORTED,
-                           "block Jacobi needs a Block-SELL operator (dense "
-                           "dof x dof node blocks, dof 2/3/4); this system "
-                           f"uses {self._format_name()}")
         if "bjacobi_minv" not in self._ws:
-            bptr, bcol, bvals, dof = self.bsell
-            minv, nbad = ops.bsell_diag_inv(bptr, bcol, bvals,
-                                            self.n // dof, dof)
-            if nbad > 0:
-                raise AcgError(ErrCode.INVALID_VALUE,
-                               f"block Jacobi: {nbad} nodes have a missing "
-                               f"or not positive definite diagonal block")
-            self._ws["bjacobi_minv"] = minv
+            self._ws["bjacobi_minv"] = self.opA.diag_inv()
         return self._ws["bjacobi_minv"]
 
     def solve_bjacobi(self, b: torch.Tensor, x: torch.Tensor,
@@ -1422,7 +1196,7 @@ class CGSolverHIP:
         the first iteration whose rr met the tolerance.  Eager (no graph
         capture)."""
         minv = self._block_inverse()
-        dof = self.bsell[3]
+        dof = self.opA.dof
         res = SolveResult(solver="cg-hip-bjacobi", maxits=maxits,
                           res_atol=res_atol, res_rtol=res_rtol,
                           nranks=self.comm.size if self.comm else 1)
@@ -1609,43 +1383,27 @@ class CGSolverHIP:
         graphs = (self._graphs.get(wskey, [None, None])
                   if graph_ok and mega else [None, None])
 
+        pipeA, pipeO = self.operators.pipe if mega else (None, None)
+
         def mega_body(wa, wb, first):
             """One megafused iteration: halo(wa) || matA pass (SpMV + update
             of interior rows), then matO pass finishing border rows."""
             have_halo = not serial
             if have_halo:
                 self._halo_fork(wa)
-            border_base = L.ninterior if L.nnzO > 0 else n
-            if self.matfree is not None:
-                nbA = S.stencil_pipe(self.matfree, n, 0, border_base, wa,
-                                     qpart, z, t, p, xi, r, wb, scal, first,
-                                     self.partials, 0, mato=False)
-            else:
-                sp, sc, sv = self.sell
-                nbA = S.sell_pipe(sp, sc, sv, n, 0, border_base, wa, qpart,
-                                  z, t, p, xi, r, wb, scal, first,
-                                  self.partials, 0, mato=False)
-            nb = nbA
+            border_base = L.ninterior if pipeO is not None else n
+            nb = pipeA.pipe(border_base, wa, qpart, z, t, p, xi, r, wb, scal,
+                            first, self.partials, 0, mato=False)
             if have_halo:
                 self._halo_join()
-            if L.nnzO > 0:
-                if self.matfree is not None:
-                    nbO = S.stencil_pipe(self.matfree, L.nborder, L.ninterior,
-                                         L.ninterior, wa, qpart, z, t, p, xi,
-                                         r, wb, scal, first, self.partials,
-                                         nbA, mato=True)
-                else:
-                    op_, oc, ov = self.sellO
-                    nbO = S.sell_pipe(op_, oc, ov, L.nborder, L.ninterior,
-                                      L.ninterior, wa, qpart, z, t, p, xi, r,
-                                      wb, scal, first, self.partials, nbA,
-                                      mato=True)
-                nb += nbO
+            if pipeO is not None:
+                nb += pipeO.pipe(L.ninterior, wa, qpart, z, t, p, xi, r, wb,
+                                 scal, first, self.partials, nb, mato=True)
             S.pipelined_finalize(self.partials, nb, scal, first)
 
-        rr_dual_ok = (rr_period > 0 and serial
-                      and L.nnzO == 0 and self.matfree is None
-                      and (self.bsell is not None or self.sell is not None))
+        opA = self.opA
+        rr_dual_ok = (rr_period > 0 and serial and L.nnzO == 0
+                      and opA.has_dual)
         rr_fast = rr_dual_ok and self._rr_fast
 
         def replace(wdst):
@@ -1653,20 +1411,9 @@ class CGSolverHIP:
             iteration gathers from."""
             with self.prof.span("replace"):
                 if rr_fast:
-                    kw = dict(ncols=self.nlocal)
-                    if self.bsell is not None:
-                        bptr, bcol, bvals, dof = self.bsell
-                        S.spmv2_bsell(bptr, bcol, bvals, n // dof, dof, xi, p,
-                                      r, t, b=b, **kw)
-                        nb = S.spmv2_bsell(bptr, bcol, bvals, n // dof, dof,
-                                           r, t, wdst, z,
-                                           partials=self.partials, **kw)
-                    else:
-                        sp, sc, sv = self.sell
-                        kw["perm"] = self.sell_perm
-                        S.spmv2_sell(sp, sc, sv, n, xi, p, r, t, b=b, **kw)
-                        nb = S.spmv2_sell(sp, sc, sv, n, r, t, wdst, z,
-                                          partials=self.partials, **kw)
+                    opA.spmv2(xi, p, r, t, b=b, ncols=self.nlocal)
+                    nb = opA.spmv2(r, t, wdst, z, partials=self.partials,
+                                   ncols=self.nlocal)
                     S.pipelined_replace_finalize(self.partials, nb, scal)
                 else:
                     self._spmv_overlapped(xi, tmp)
@@ -1680,13 +1427,7 @@ class CGSolverHIP:
                         # fast path switched off (_rr_fast): the dots in
                         # the dual kernels' summation order, so the two
                         # paths give the same gamma / delta bit for bit
-                        if self.bsell is not None:
-                            dof = self.bsell[3]
-                            nb = S.dot2_slices(r, wdst, n // dof, dof,
-                                               self.partials)
-                        else:
-                            nb = S.dot2_slices(r, wdst, n, 1, self.partials,
-                                               perm=self.sell_perm)
+                        nb = opA.dot2_slices(r, wdst, self.partials)
                         S.pipelined_replace_finalize(self.partials, nb, scal)
         # lag-1 convergence pipeline: gamma_k is copied to the host as soon
         # as its allreduce lands, but the host *reads* it one iteration

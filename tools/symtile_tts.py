@@ -62,8 +62,8 @@ def one_grid(G, dof, dev, reps, its, iters, qmax):
     sym = CGSolverHIP(S, device=dev, force_format="bsell-st")
     if qmax != sym.bsell_st.qmax:
         bptr, bcol, bvals, _ = S.A_bsell
-        sym.bsell_st = bsell_st_build(bptr, bcol, bvals, n // dof, dof,
-                                      S.node_order, qmax=qmax)
+        sym.opA.st = bsell_st_build(bptr, bcol, bvals, n // dof, dof,
+                                    S.node_order, qmax=qmax)
         assert sym.bsell_st is not None, "gate refused this qmax"
     st = sym.bsell_st
     out.update(qmax=st.qmax, byte_ratio=st.ratio, stored_bytes=st.stored_bytes,
